@@ -21,7 +21,19 @@ process touches the GPU, and relays rank 0's JSON line; under an external launch
 (WORLD_SIZE set) it is one rank.  Envs shard by global id: rank r owns env ids
 [r*N, (r+1)*N).
 
-Extra JSON fields:
+A plain run sets up, warms up, times `--steps` iterations, writes `--dump-outputs DIR` if given
+and prints the result line (metric, value, ms_per_step, the workload and per-iteration times).
+Everything else the benchmark measures takes runs of its own after the timed region and is
+behind `--full`: the two kernels' rooflines, the rollout's wall time per step and the CPU baseline.
+
+`--dump-outputs DIR` (rank 0): what the last timed `Algo_PPO.train(1)` left its caller, written
+right after the timed region: the six nets' flat weights (`actor_net_cross.npy` ...
+`critic_net_choice.npy`, float32) and the last iteration's reward-curve entries
+(`reward_curves.npy`: cross, wait, choice means, NaN for an empty bucket; `scenario_balance.npy`:
+cross and wait row counts; float64).  Envs, nets and policy noise are seeded, so two runs with
+the same arguments start from identical inputs.
+
+Extra JSON fields with `--full`:
   roofline     — the dominant kernel, the fused continuous-head train kernel (k_mlp_train,
                  ~85 % of GPU time): algorithmic FLOPs per row x rows /
                  launch duration, from HIP events on its stream around each launch of one
@@ -107,7 +119,13 @@ def parse():
                     help="BASELINE.json config: 3 = 4cars 4/1/2 (the metric), 4 = scalable 8/1/4, 2 = coop 2/1/2")
     ap.add_argument("--envs", type=int, default=None,
                     help="envs per GPU (default: BASELINE.json's for the config: 4096 for config 2, else 65536)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the kernels' rooflines, the rollout's wall time "
+                         "per step and the CPU baseline (runs of their own; off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed iteration left its caller (nets, reward-curve "
+                         "entries) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-envs", type=int, default=4096)
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL, one GPU per rank); gloo only to rehearse several ranks on one GPU")
@@ -206,8 +224,6 @@ def main():
 
     for _ in range(a.warmup):
         iteration()
-    from mhppo import _lib
-    L = _lib.lib()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -230,6 +246,57 @@ def main():
     ms = dt / a.steps * 1e3
     iter_ms = [round(marks[k].elapsed_time(marks[k + 1]), 3) for k in range(a.steps)]
     value = world * N * T / (dt / a.steps)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, algo)
+    if rank == 0 and a.save_nets:
+        import numpy as np
+        np.save(a.save_nets, np.concatenate([net.flat().cpu().numpy() for net in algo.nets()]))
+    agents = "ragged 1-8 existing of 8 slots" if variant == "scalable" else venv.n_slots
+    line = {
+        "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64 env / f32 nets", "data": "synthetic (random-init Model_PPO heads, CPython-MT19937 env streams, "
+                                            "Philox policy noise)",
+        "config": {"workload": f"config {a.config}: {variant} nb_car={nc} nb_ped={npd} nb_lines={nl}, {N} envs/GPU x "
+                               f"80 steps, full PPO iteration (rollout + returns + 10+10 epochs)",
+                   "envs_per_gpu": N, "agents": agents, "T": T, "parallelism": f"dp{world}"},
+        "dist": {"world_size": world, "backend": (a.dist_backend if dist.is_initialized() else None),
+                 "env_ranges": [[r * N, (r + 1) * N] for r in range(world)],
+                 "collectives": "forced (one rank)" if a.force_collectives and world == 1 else
+                 ("per epoch: advantage sums + gradient bucket" if world > 1 else "none (one rank)")},
+        "iter_ms": iter_ms,
+    }
+    if a.full:
+        line.update(full_measurements(algo, venv, ppo, iteration, variant, npd, N, T))
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(a, variant, nc, npd, nl)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, algo):
+    """What the last timed Algo_PPO.train(1) left its caller: every net's flat weights (float32)
+    and the last iteration's reward-curve entries (float64; NaN where a bucket was empty)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = ("actor_net_cross", "actor_net_wait", "actor_net_choice",
+             "critic_net_cross", "critic_net_wait", "critic_net_choice")
+    for name, net in zip(names, algo.nets()):
+        np.save(os.path.join(path, name + ".npy"), net.flat().detach().cpu().numpy().astype(np.float32))
+    cross, wait, choice, balance = algo.curves()
+    m_c, m_w = balance[-1]
+    np.save(os.path.join(path, "reward_curves.npy"),
+            np.array([cross[-1] if m_c > 0 else np.nan, wait[-1] if m_w > 0 else np.nan, choice[-1]], np.float64))
+    np.save(os.path.join(path, "scenario_balance.npy"), np.array([m_c, m_w], np.float64))
+
+
+def full_measurements(algo, venv, ppo, iteration, variant, npd, N, T):
+    """--full: the fields `roofline`, `roofline_env` and `rollout_step_us` (module docstring)."""
+    from mhppo import _lib
+    L = _lib.lib()
     # After the timed region (same process, same workload): (0) one more training iteration with the
     # train passes on ONE stream and torch events around each launch -> roofline (the product runs
     # the heads' passes on two streams, where one launch's events would span the other's kernel);
@@ -283,19 +350,7 @@ def main():
     traffic = (pmc_traffic(("k_mlp_train_x3<0", "Geo<16, 1, 13"), ("k_mlp_train_x3<1", "Geo<16, 1, 13")) if split else
                pmc_traffic("k_mlp_train<0, 7, true>", "k_mlp_train<1, 7, true>", required=False))
     traffic_env = pmc_traffic("k_sample_env")
-    agents = "ragged 1-8 existing of 8 slots" if variant == "scalable" else S
-    line = {
-        "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64 env / f32 nets", "data": "synthetic (random-init Model_PPO heads, CPython-MT19937 env streams, "
-                                            "Philox policy noise)",
-        "config": {"workload": f"config {a.config}: {variant} nb_car={nc} nb_ped={npd} nb_lines={nl}, {N} envs/GPU x "
-                               f"80 steps, full PPO iteration (rollout + returns + 10+10 epochs)",
-                   "envs_per_gpu": N, "agents": agents, "T": T, "parallelism": f"dp{world}"},
-        "dist": {"world_size": world, "backend": (a.dist_backend if dist.is_initialized() else None),
-                 "env_ranges": [[r * N, (r + 1) * N] for r in range(world)],
-                 "collectives": "forced (one rank)" if a.force_collectives and world == 1 else
-                 ("per epoch: advantage sums + gradient bucket" if world > 1 else "none (one rank)")},
+    return {
         "roofline": {"bound": "mfma",
                      "kernel": ("k_mlp_train_x3 (fused continuous-head fwd/loss/bwd/wgrad, bf16x3-split MFMA, "
                                 "f32-equivalent FLOPs)" if split else
@@ -321,18 +376,7 @@ def main():
                                     "one_chain = policy + env-step launches, parts = those on two streams "
                                     "(env halves), product = the product's collect (its step loop replays a "
                                     "captured HIP graph at small N)"},
-        "iter_ms": iter_ms,
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(a, variant, nc, npd, nl)
-    if rank == 0 and a.save_nets:
-        import numpy as np
-        np.save(a.save_nets, np.concatenate([net.flat().cpu().numpy() for net in algo.nets()]))
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

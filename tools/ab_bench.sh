@@ -11,7 +11,7 @@ for r in $(seq $REPS); do
   for v in "$@"; do
     if [ "$v" = base ]; then lib=""; else lib="build_ab/$v/libmhppo.so"; fi
     f=$O/ab_${v}_cfg${CFG}_$r.json
-    MHPPO_LIB=$lib timeout -k 10 300 python -u bench.py --config $CFG --no-cpu-baseline > $f 2> $O/ab_${v}_$r.err || { tail -20 $O/ab_${v}_$r.err; exit 1; }
+    MHPPO_LIB=$lib timeout -k 10 300 python -u bench.py --full --config $CFG --no-cpu-baseline > $f 2> $O/ab_${v}_$r.err || { tail -20 $O/ab_${v}_$r.err; exit 1; }
     python3 -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]);r=d['roofline'];e=d['roofline_env'];it=d['iter_ms'];print(sys.argv[2], round(d['ms_per_step'],3), 'ms', round(d['value']/1e6,2), 'M/s train', round(r['launch_ms'],4), 'ms env', round(e['kernel_ms']*1e3,2), 'us iters', min(it), '..', max(it))" $f "$v#$r" | tee -a $O/ab_summary.txt
   done
 done

@@ -5,7 +5,7 @@
 # steps (each under its own time limit; the first failure ends the session):
 #   tests[=file:file...]   pytest -m gpu (all GPU tests, or the listed files under tests/)
 #   smoke                  __graft_entry__.smoke()
-#   bench=<cfg>[:<n>]      bench.py --config <cfg> (n repeats, one summary line each; cfg 3 with cpu_baseline
+#   bench=<cfg>[:<n>]      bench.py --full --config <cfg> (n repeats, one summary line each; cfg 3 with cpu_baseline
 #                          only when named "bench=3full")
 #   ab=<v>:<v>...          tools/ab_x3.sh over the A/B library variants (AB_ARGS passed through)
 #   mlp                    tools/bench_mlp_train.py (AB_ARGS passed through) on the in-tree library
@@ -35,7 +35,7 @@ for arg in "$@"; do for step in ${arg//,/ }; do
       extra="--no-cpu-baseline"; [ "$cfg" = 3full ] && { cfg=3; extra=""; }
       for i in $(seq $n); do
         f=$O/bench_cfg${cfg}_$i.json
-        timeout -k 10 400 python -u bench.py --config $cfg $extra > $f 2> $O/bench_cfg${cfg}_$i.err || { tail -20 $O/bench_cfg${cfg}_$i.err; exit 1; }
+        timeout -k 10 400 python -u bench.py --full --config $cfg $extra > $f 2> $O/bench_cfg${cfg}_$i.err || { tail -20 $O/bench_cfg${cfg}_$i.err; exit 1; }
         summ $f "cfg$cfg#$i" | tee -a $O/summary.txt
       done ;;
     ab)

@@ -12,9 +12,9 @@ if [ "$WHAT" = tests ] || [ "$WHAT" = all ]; then
   tail -1 $OUT/smoke.log
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH FAILED; tail -30 $OUT/bench.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH FAILED; tail -30 $OUT/bench.err; exit 1; }
   cat $OUT/bench.json
-  timeout -k 10 400 python -u bench.py --config 4 --no-cpu-baseline > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err || { echo BENCH4 FAILED; tail -30 $OUT/bench_cfg4.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config 4 --no-cpu-baseline > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err || { echo BENCH4 FAILED; tail -30 $OUT/bench_cfg4.err; exit 1; }
   cat $OUT/bench_cfg4.json
 fi
 if [ "$WHAT" = prof ] || [ "$WHAT" = all ]; then
