@@ -1,4 +1,4 @@
-"""Build-time ISA check of the split-precision train kernel's in-gap LDS reads (csrc/mlp_train.hip
+"""Build-time ISA check of the split-precision train kernel's in-gap LDS reads (csrc/mlp_x3_prims.h
 X3_MACC6_RD).
 
 Those inline-asm blocks issue six ds_read_b64_tr_b16 between their MFMAs and hand the

@@ -13,8 +13,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "mh-ppo_amd")]
 from mhppo import _lib, ppo  # noqa: E402
 from mhppo.models import Model_PPO  # noqa: E402
 
-# the hand-placed passes (SCH, the default): marks after each MFMA block of Pass::fwd_s / bwd_s;
-# MHPPO_X3_SCH=0 builds: the phase-by-phase marks
+# the hand-placed passes (the 13-input single-net ones): marks after each MFMA block of Pass::fwd_s /
+# bwd_s; the phase-by-phase marks exist only for the passes that are not hand-placed (the fused pair,
+# the choice heads' nets)
 PH_SCH = {1: "tile inputs wait", 2: "layer 1 (+h1 s0 split)", 3: "layer 2 (+payload)", 4: "layer 3 (+payload)",
           5: "loss + d3 + d3 s0 split", 6: "A dH2 (+payload)", 7: "B dW3 (+payload)", 8: "C dH1 (+payload)",
           9: "D dW2 (+payload)"}  # E (dW1) runs in the next tile's layer 1
