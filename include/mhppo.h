@@ -284,6 +284,51 @@ int mhppo_bucket_scatter(const int64_t *pos, const int8_t *bucket, int64_t NS, i
                          const float *act_tm, const float *logp_tm, const float *ret_tm, const double *rew_tm,
                          const mhppo_bucket_dst *dst, void *stream);
 
+/* mhppo_bucket_scatter that also adds to rew_sums[b] the float64 sum of (double)(float)rew over
+ * bucket b's rows (the reward curves' sums, Algo_PPO.train :886-892): per-block partials folded in
+ * a fixed order (deterministic, no atomics; the caller zeroes rew_sums, or mhppo_bucket_plan has).
+ * dst[0] and dst[1] may name the same buffers (both buckets in one shared buffer: bucket[] then
+ * only keys the sums).  work: mhppo_bucket_work_bytes(NS, T) bytes of device scratch, 8-byte
+ * aligned. */
+int mhppo_bucket_scatter_sums(const int64_t *pos, const int8_t *bucket, int64_t NS, int32_t T, const float *obs_tm,
+                              const float *act_tm, const float *logp_tm, const float *ret_tm, const double *rew_tm,
+                              const mhppo_bucket_dst *dst, double *rew_sums, void *work, void *stream);
+
+/* The bucket plan (bucket_segments; Coop-MH-PPO-scalable.py:489-507): everything the bucketing
+ * decides per (env, slot) segment s < NS = N*S, on the device, in three launches (per-block counts,
+ * a one-block scan of them, placement: no block waits on another) before the caller's one read of
+ * `info`.
+ * In: a_d int32 [N, S*P] (the choice actions), closest int32 [NS] (each car's closest pedestrian),
+ * exist uint8 [NS], rec_of int32 [NS] or NULL (the compact record layout: segment s's record index,
+ * < 0 = none), ep_min float64 [NS], feat_d float32 [NS*P, dc], logp_d float32 [NS*P], fix_bucket,
+ * status int32 [1] or NULL (the rollout's NaN-flag word, copied to info).
+ * Bucket rule: only existing segments; segment s = (env n, slot i) is cross when action_d[i] <= 0,
+ * action_d = 2 a_d[n] - 1 indexed by the CAR index i, or with fix_bucket by the car's
+ * own closest pedestrian, a_d[s*P + closest[s]]; wait otherwise.
+ * Out: pos int64 [NS] / bucket int8 [NS] as mhppo_bucket_scatter takes them (per record when
+ * rec_of is given): cross segments ranked from 0 in (env, slot) order, bucket 0; wait segments
+ * ranked from w0 = (n_cross + 3) / 4 * 4, bucket 1 — positions in ONE shared buffer of
+ * (NS + 3) * T rows; everything else pos -1, bucket 0.
+ * The choice batch, existing segments first in (env, slot) order, row k taken at
+ * b = s*P + closest[s] of the k-th existing segment s: c_obs [., dc] = feat_d[b], c_act int32 =
+ * a_d[b], c_logp = logp_d[b], c_ret = (float)ep_min[s]; caller-sized for NS rows, rows >= n_all
+ * are not written.
+ * info (device): the sizes, the status word, counts = the existing segments with c_act == 0 / == 1,
+ * rew_sums[2] = the float64 sum of c_ret (per-block partials, fixed order); rew_sums[0..1] are
+ * zeroed for mhppo_bucket_scatter_sums to add the cross / wait sums.
+ * work: mhppo_bucket_work_bytes(NS, T) bytes of device scratch, 8-byte aligned. */
+typedef struct {
+  int64_t n_cross, n_wait, n_all, status;
+  double counts[2];
+  double rew_sums[3];
+} mhppo_bucket_info;
+int64_t mhppo_bucket_work_bytes(int64_t NS, int32_t T);
+int mhppo_bucket_plan(int64_t N, int32_t S, int32_t P, int32_t dc, const int32_t *a_d, const int32_t *closest,
+                      const uint8_t *exist, const int32_t *rec_of, const double *ep_min, const float *feat_d,
+                      const float *logp_d, int32_t fix_bucket, const int32_t *status, int64_t *pos, int8_t *bucket,
+                      float *c_obs, int32_t *c_act, float *c_logp, float *c_ret, mhppo_bucket_info *info,
+                      void *work, void *stream);
+
 /* Advantage statistics of A = G - V over M rows: stats float64 [2] += (sum A, sum A^2)
  * (caller zeroes it; partial sums all-reduce across ranks).  Normalisation
  * A' = (A - mean) / (std_unbiased + 1e-10) with mean/std from (stats, M_global). */

@@ -87,6 +87,9 @@ _SIGS = {
     "mhppo_returns_scan": (I32, [P, P, I64, I32, F64, P]),
     "mhppo_returns_scan_tm": (I32, [P, P, I64, I32, F64, P]),
     "mhppo_bucket_scatter": (I32, [P, P, I64, I32] + [P] * 7),
+    "mhppo_bucket_scatter_sums": (I32, [P, P, I64, I32] + [P] * 9),
+    "mhppo_bucket_work_bytes": (I64, [I64, I32]),
+    "mhppo_bucket_plan": (I32, [I64, I32, I32, I32] + [P] * 7 + [I32] + [P] * 10),
     "mhppo_adv_stats": (I32, [P, P, I64, P, P]),
     "mhppo_adv_normalize": (I32, [P, P, I64, P, F64, P, P]),
     "mhppo_ppo_cont_fwd_bwd": (I32, [P, P, P, P, I64, F64, P, P, P]),

@@ -270,9 +270,15 @@ class Algo_PPO:
                                          self.cov_mat, self.cov_mat_d, self.batch_size, forced_choice=fc,
                                          eps_tape=et)
             m_c, m_w, m_d = self.update()
-            rc, rw, rd = self.rollout.immediate_rewards()
             dev = self.venv.device
-            sums = torch.stack([rc.double().sum(), rw.double().sum(), rd.double().sum()]).to(dev)
+            # the reward curves' sums over (cross, wait, choice): from the bucketing pass on the GPU
+            # (bucket_segments: fixed-order float64 partials), else torch reductions
+            sums = (self.rollout.choice or {}).get("rew_sums")
+            if sums is None:
+                rc, rw, rd = self.rollout.immediate_rewards()
+                sums = torch.stack([rc.double().sum(), rw.double().sum(), rd.double().sum()]).to(dev)
+            elif ppo._dp():
+                sums = sums.clone()  # the all-reduce below is in place
             ppo._allreduce_(sums)
             if dev.type == "cuda":
                 # the reward curves take the sums without a host sync here: an asynchronous copy to

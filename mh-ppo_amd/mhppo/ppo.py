@@ -455,9 +455,14 @@ def train_epochs(heads, n_epochs, bucket=None):
     of epoch e + 1 the critic's weights after its Adam step e; each optimiser steps n_epochs
     times.  Returns this rank's (actor, critic) loss sums of the last epoch per head.
     The launches go straight through the C-ABI with each head's arguments resolved once
-    (_HeadPlan); an empty head (M == 0) runs k_mlp_train's empty-shard path."""
+    (_HeadPlan); an empty head (M == 0) runs k_mlp_train's empty-shard path.
+    The float64 sums of all steps are one tensor [n_epochs + 1, 2 H, 3] (one fill, not one per
+    step), and without data parallelism a head's advantage sums are read where its critic pass
+    left them (all_sums[k - 1, i, 1:3], two contiguous doubles: no copy)."""
     H = len(heads)
     dev = heads[0].obs.device
+    all_sums = torch.zeros(n_epochs + 1, 2 * H, 3, dtype=torch.float64, device=dev)
+    dp = _dp()
     paired = [_use_pair(h) for h in heads]
     plans = [_HeadPlan(h) if h.obs.shape[0] > 0 else None for h in heads]
     main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
@@ -466,7 +471,7 @@ def train_epochs(heads, n_epochs, bucket=None):
     stats = None        # all-reduced advantage sums of the previous step's critic passes [2H]
     out = [[None, None] for _ in range(H)]
     for k in range(n_epochs + 1):
-        sums = torch.zeros(2 * H, 3, dtype=torch.float64, device=dev)  # critic rows, actor rows
+        sums = all_sums[k]  # critic rows, actor rows
         crit = k < n_epochs
         trained = []
         if side:  # the side streams start after this step's inputs (Adam, sums, stats) on main
@@ -481,7 +486,9 @@ def train_epochs(heads, n_epochs, bucket=None):
             ctx = torch.cuda.stream(sti) if sti is not None else contextlib.nullcontext()
             st = sti.cuda_stream if sti is not None else None
             with ctx:
-                stp = stats[2 * i:2 * i + 2] if k > 0 else None
+                stp = None
+                if k > 0:  # the previous step's critic pass sums (all-reduced under data parallelism)
+                    stp = stats[2 * i:2 * i + 2] if dp else all_sums[k - 1, i, 1:3]
                 if p is None:  # an empty shard: zero gradients, sums unchanged (k_mlp_train's M == 0 path)
                     if k > 0:
                         cont = h.kind == "c"
@@ -510,7 +517,7 @@ def train_epochs(heads, n_epochs, bucket=None):
                     out[i][1] = sums[i, 0:1]
         for sd in side:  # join
             main.wait_stream(sd)
-        if crit:
+        if crit and dp:  # the all-reduce needs one span
             stats = sums[:H, 1:3].reshape(-1).contiguous()
             _allreduce_(stats)
         if bucket is not None:
