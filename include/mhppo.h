@@ -396,6 +396,47 @@ int mhppo_mlp_train_pair(const float *packed_actor, const float *packed_critic, 
 int mhppo_mse_fwd_bwd(const float *value, const float *ret, int64_t M, double inv_m, float *dv,
                       double *loss, void *stream);
 
+/* ---- batched head forward and PPO diagnostics (csrc/mlp_infer.hip; opt-in, beyond the reference) ---- */
+
+/* Forward of one Model_PPO head over M rows in the rollout's arithmetic (bit-identical to what
+ * mhppo_rollout_begin / _policy compute for the same feature row and weights): every output is
+ * the ascending-k float32 fmaf chain from 0 with the bias added last, on f32 MFMA in 32-row tiles,
+ * then the head's finish (kind 1: tanh * std + mean; kind 2: pairwise softmax).  Replaces
+ * Model_PPO.forward (Coop-MH-PPO-scalable.py:69-93) on a batch, without autograd.
+ * X float32 [M, n_in], n_in <= 64 (any 4-byte alignment); out float32 [M] (kind 0: V, kind 1: mu)
+ * or [M, 2] (kind 2: probs).  M == 0 launches nothing.  MHPPO_EINVAL: n_in outside 1..64, a
+ * kind / n_out mismatch (kinds 0 and 1: n_out 1, kind 2: n_out 2), a NULL pointer. */
+int mhppo_mlp_forward(const mhppo_mlp *net, const float *X, int64_t M, float *out, void *stream);
+
+/* PPO diagnostics of one head over M rows of its batch: the actor's and the critic's forward (one
+ * load of X per tile, both nets' weights resident in LDS) and float64 sums of the per-row terms
+ * below; no per-row output.  With logp_new the actor's log-probability of the taken action
+ * (kind 1: MVN(mu, 0.5).log_prob(act); kind 2: log clamp(p_a / (p0 + p1), eps, 1 - eps), both as
+ * the rollout computes them) and V the critic's output.  The reference has no counterpart (it
+ * prints reward averages only, :894-906); the quantities are the usual PPO monitors of
+ * train_model_c / _d's ratio (:795-806, :834-842) and critics. */
+#define MHPPO_DIAG_DSUM   0  /* sum d                           d = logp_new - logp_old          */
+#define MHPPO_DIAG_K3     1  /* sum (expm1(d) - d)              >= 0, the low-variance KL estimate */
+#define MHPPO_DIAG_CLIP   2  /* rows with ratio outside [0.8, 1.2], as a double                    */
+#define MHPPO_DIAG_RATIO  3  /* sum exp(d)                                                         */
+#define MHPPO_DIAG_ENT    4  /* kind 2: sum of the policy entropy; kind 1: 0                       */
+#define MHPPO_DIAG_E      5  /* sum (G - V)                                                        */
+#define MHPPO_DIAG_E2     6  /* sum (G - V)^2                                                      */
+#define MHPPO_DIAG_G      7  /* sum G                                                              */
+#define MHPPO_DIAG_G2     8  /* sum G^2                                                            */
+#define MHPPO_DIAG_V      9  /* sum V                                                              */
+#define MHPPO_DIAG_N     10
+/* Bytes of device scratch (8-byte aligned) mhppo_ppo_diag needs for M rows (>= 8). */
+int64_t mhppo_ppo_diag_work_bytes(int64_t M);
+/* actor->kind 1: act float32 [M]; actor->kind 2: act int32 [M]; critic->kind 0, same n_in as the actor.
+ * sums float64 [MHPPO_DIAG_N] is WRITTEN (this rank's rows; the sums add across ranks): per-block
+ * float64 partials folded in a fixed order (no atomics: the same call gives the same bits).
+ * M == 0 writes zeros and launches nothing else.  MHPPO_EINVAL as mhppo_mlp_forward, and for
+ * actor and critic of different n_in or an actor of kind 0 / a critic of another kind. */
+int mhppo_ppo_diag(const mhppo_mlp *actor, const mhppo_mlp *critic, const float *X, int64_t M,
+                   const void *act, const float *logp_old, const float *ret, double *sums,
+                   void *work, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

@@ -97,6 +97,9 @@ _SIGS = {
     "mhppo_mse_fwd_bwd": (I32, [P, P, I64, F64, P, P, P]),
     "mhppo_mlp_train": (I32, [I32, I32, P, P, I64, P, P, P, P, P, P, F64, ctypes.c_float, ctypes.c_float, P, P, P]),
     "mhppo_mlp_train_pair": (I32, [P, P, P, I64, P, P, P, P, P, F64, ctypes.c_float, ctypes.c_float, P, P, P, P, P]),
+    "mhppo_mlp_forward": (I32, [ctypes.POINTER(Mlp), P, I64, P, P]),
+    "mhppo_ppo_diag_work_bytes": (I64, [I64]),
+    "mhppo_ppo_diag": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, I64, P, P, P, P, P, P]),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }

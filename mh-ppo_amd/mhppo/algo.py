@@ -168,6 +168,18 @@ class Algo_PPO:
         self.ep_scenario_balance = []
         self._pending_curves = []  # (pinned sums, event, m_c, m_w, m_d) not yet appended
         self.last_losses = {}
+        # Opt-in per-iteration PPO diagnostics (Algo_PPO(diagnostics=True, diagnostics_every=k)):
+        # after the update of every k-th iteration one forward-only launch per trained head
+        # (mhppo.ppo.k_ppo_diag) over that iteration's batch with the post-update nets; the entries
+        # {"iteration": i, "cross": {...}, "wait": {...}, "choice": {...}} (mhppo.ppo.diag_stats;
+        # only the heads trained that iteration) land in self.diagnostics like the reward curves,
+        # without a host sync in the iteration.  Not checkpointed: save_checkpoint keeps the
+        # reward curves only, and a resumed run starts with an empty list.
+        self._diag_on = bool(self.diagnostics)
+        self.diagnostics = []
+        self._pending_diag = []   # (pinned [H, DIAG_N] sums, event, iteration, [(name, m, kind)])
+        self._diag_heads = None   # update()'s (name, Head) list of the current iteration
+        self._diag_work = {}      # per head name: the launch's scratch, allocated once
 
     def nets(self):
         return [self.actor_net_cross, self.actor_net_wait, self.actor_net_choice, self.critic_net_cross,
@@ -194,6 +206,10 @@ class Algo_PPO:
         self.exact_f32 = False
         # reward curves written to load_model/parameters at the end of train() (:908-916)
         self.save_curves = True
+        # per-iteration diagnostics (approximate KL, clip fraction, entropy, explained variance),
+        # every diagnostics_every-th iteration; off: the iteration runs exactly the code it always did
+        self.diagnostics = False
+        self.diagnostics_every = 1
         for k, v in hyperparameters.items():
             setattr(self, k, v)
 
@@ -234,6 +250,8 @@ class Algo_PPO:
                                       counts, per_row=self.fix_choice_loss, exact=self.exact_f32))
                 names.append("choice")
             losses = ppo.train_epochs(heads, 10, self.grad_bucket) if heads else None
+            if getattr(self, "_diag_on", False):
+                self._diag_heads = list(zip(names, heads))
         if self.verbose and losses is not None:
             div = {"cross": (m_c, m_c), "wait": (m_w, m_w), "choice": (m_d * m_d, m_d)}
             if self.fix_choice_loss:
@@ -271,6 +289,9 @@ class Algo_PPO:
                                          eps_tape=et)
             m_c, m_w, m_d = self.update()
             dev = self.venv.device
+            diag = getattr(self, "_diag_on", False)
+            if diag and self.total_loop % max(1, int(self.diagnostics_every)) == 0:
+                self._queue_diagnostics()
             # the reward curves' sums over (cross, wait, choice): from the bucketing pass on the GPU
             # (bucket_segments: fixed-order float64 partials), else torch reductions
             sums = (self.rollout.choice or {}).get("rew_sums")
@@ -303,7 +324,11 @@ class Algo_PPO:
             self.total_loop = self.total_loop + 1
             if len(self._pending_curves) > 1:  # the previous iteration's sums landed long ago
                 self._flush_curves(keep_last=True)
+            if diag and len(self._pending_diag) > 1:
+                self._flush_diagnostics(keep_last=True)
         self._flush_curves()
+        if getattr(self, "_diag_on", False):
+            self._flush_diagnostics()
         if _rank() == 0 and self.save_curves:
             self.save_reward_curves()
         if self.verbose and _rank() == 0:
@@ -325,9 +350,45 @@ class Algo_PPO:
             self.ep_scenario_balance.append([int(m_c), int(m_w)])
         del self._pending_curves[:n]
 
+    def _queue_diagnostics(self):
+        """One diagnostics launch per head update() just trained (post-update nets, this
+        iteration's buckets), one all-reduce of the stacked sums under data parallelism, and an
+        asynchronous copy to pinned memory (appended by _flush_diagnostics once it has landed)."""
+        heads = self._diag_heads or []
+        if not heads:
+            return
+        dev = self.venv.device
+        with torch.cuda.device(dev):
+            rows = []
+            for name, h in heads:
+                h._diag_work = self._diag_work.get(name)
+                rows.append(ppo.k_ppo_diag(h))
+                self._diag_work[name] = h._diag_work
+            sums = torch.stack(rows)  # [H, DIAG_N]
+            ppo._allreduce_(sums)
+            host = torch.empty(sums.shape, dtype=torch.float64, pin_memory=True)
+            host.copy_(sums, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+        self._pending_diag.append((host, ev, int(self.total_loop), [(name, h.m, h.kind) for name, h in heads]))
+
+    def _flush_diagnostics(self, keep_last=False):
+        """Append the diagnostics entries whose sums have been read back."""
+        n = len(self._pending_diag) - (1 if keep_last else 0)
+        for host, ev, it, heads in self._pending_diag[:n]:
+            ev.synchronize()
+            entry = {"iteration": it}
+            for row, (name, m, kind) in zip(host.tolist(), heads):
+                entry[name] = ppo.diag_stats(row, m, entropy=(kind == "d"))
+            self.diagnostics.append(entry)
+        del self._pending_diag[:n]
+
     def curves(self):
-        """The reward curves with every pending entry appended: (cross, wait, choice, balance)."""
+        """The reward curves with every pending entry appended: (cross, wait, choice, balance).
+        (Also lands every pending entry of self.diagnostics.)"""
         self._flush_curves()
+        if getattr(self, "_diag_on", False):
+            self._flush_diagnostics()
         return self.ep_reward_cross, self.ep_reward_wait, self.ep_reward_choice, self.ep_scenario_balance
 
     def _curve_path(self, name):
@@ -379,7 +440,8 @@ class Algo_PPO:
 
     def save_checkpoint(self, path):
         """Everything needed to continue training bit-identically.  Under data parallelism
-        every rank writes `path.rank<r>` (its env shard differs; nets/Adam are replicated)."""
+        every rank writes `path.rank<r>` (its env shard differs; nets/Adam are replicated).
+        The opt-in diagnostics (self.diagnostics) are not part of it: the format is unchanged."""
         self._flush_curves()  # the newest iteration's curve entries may still be in flight
         ck = {
             "nets": {f"{k}_{h}": getattr(self, f"{k}_net_{h}").state_dict() for h in ("cross", "wait", "choice")

@@ -127,6 +127,26 @@ class Model_PPO(nn.Module):
             return torch.add(torch.mul(self.return_layer(out), self.std), self.mean)
         return self.layer4(a3)
 
+    def forward_rows(self, x):
+        """The head's forward over a batch on the native path (mhppo_mlp_forward), without autograd:
+        x float32 [M, n_in] on the model's GPU -> [M] (model_type 0: V, 1: mu) or [M, 2] (2: probs).
+        The rollout's arithmetic (ascending-k fmaf chains, glibc tanhf / expf): for a feature row
+        the rollout saw with these weights the result equals the rollout's bit for bit, which
+        `forward` (torch's GEMMs and vectorised tanh / exp) does not."""
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.n_in:
+            raise ValueError(f"forward_rows takes a float32 [M, {self.n_in}] tensor")
+        w = self.flat()
+        if x.device.type != "cuda" or x.device != w.device:
+            raise ValueError("forward_rows runs on the model's GPU: x must live there (there is no CPU path)")
+        x = x.detach().contiguous()
+        M = x.shape[0]
+        out = torch.empty((M, 2) if self.model_type == 2 else (M,), dtype=torch.float32, device=x.device)
+        d, keep = self.mlp_desc()
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().mhppo_mlp_forward(ctypes.byref(d), _lib.ptr(x), M, _lib.ptr(out),
+                                                    _lib.stream_ptr()))
+        return out
+
     @property
     def n_in(self):
         return self.layer1.in_features

@@ -27,6 +27,8 @@ gradient is the full-batch gradient; Adam then runs replicated.  A rank whose sh
 of a head is empty still joins both collectives (the kernel writes a zero gradient).
 """
 import contextlib
+import ctypes
+import math
 import os
 
 import torch
@@ -282,6 +284,61 @@ def k_mlp_train_pair(actor, critic, obs, ret, value, act, logp_old, stats, m_glo
         ev[1].record()
         TRAIN_EVENTS.append((3, 13, M, ev[0], ev[1]))  # kind 3: a fused pair launch (two passes)
     return ga, gc, value
+
+
+# ---------------------------------------------------------------- diagnostics
+# mhppo_ppo_diag (include/mhppo.h MHPPO_DIAG_*): float64 sums over a head's batch
+DIAG_DSUM, DIAG_K3, DIAG_CLIP, DIAG_RATIO, DIAG_ENT, DIAG_E, DIAG_E2, DIAG_G, DIAG_G2, DIAG_V = range(10)
+DIAG_N = 10
+
+
+def k_ppo_diag(head):
+    """This rank's float64 [DIAG_N] diagnostic sums of one Head (mhppo_ppo_diag): the actor's and
+    the critic's forward over head.obs with their current weights, against the batch's recorded
+    act / logp / ret.  Forward only, one launch plus the fold, on the current stream; nothing is
+    synchronised.  The scratch is allocated once per head (head._diag_work) and reused."""
+    actor, critic = head.actor, head.critic
+    want = 1 if head.kind == "c" else 2
+    if actor.model_type != want or critic.model_type != 0:
+        raise ValueError(f"a kind {head.kind!r} head has a model_type {want} actor and a model_type 0 critic")
+    dev = head.obs.device
+    obs = head.obs.float().contiguous()
+    M = obs.shape[0]
+    act = head.act.float().contiguous() if head.kind == "c" else head.act.to(torch.int32).contiguous()
+    logp, ret = head.logp.float().contiguous(), head.ret.float().contiguous()
+    L = _lib.lib()
+    need = max(1, (int(L.mhppo_ppo_diag_work_bytes(M)) + 7) // 8)
+    work = getattr(head, "_diag_work", None)
+    if work is None or work.numel() < need or work.device != dev:
+        work = head._diag_work = torch.empty(need, dtype=torch.float64, device=dev)
+    sums = torch.empty(DIAG_N, dtype=torch.float64, device=dev)
+    da, ka = actor.mlp_desc()
+    dc, kc = critic.mlp_desc()
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        _lib.check(L.mhppo_ppo_diag(ctypes.byref(da), ctypes.byref(dc), p(obs), M, p(act), p(logp), p(ret), p(sums),
+                                    p(work), _lib.stream_ptr()))
+    return sums
+
+
+def diag_stats(sums, m, entropy=True):
+    """The per-iteration diagnostics of one head from its GLOBAL sums (a sequence of DIAG_N floats:
+    all ranks' k_ppo_diag sums added) and global row count m.  A pure function.
+    approx_kl: mean of expm1(d) - d, d = logp_new - logp_old (>= 0; the low-variance estimate of
+    KL(old || new)); kl_k1 = -mean d; clip_frac: the rows whose ratio left [0.8, 1.2]; ratio_mean;
+    entropy (choice head only: entropy=True); value_mse = mean (G - V)^2; explained_var =
+    1 - Var(G - V) / Var(G), NaN when the returns have no variance."""
+    s = [float(x) for x in sums]
+    m = float(m)
+    out = {"approx_kl": s[DIAG_K3] / m, "kl_k1": -s[DIAG_DSUM] / m, "clip_frac": s[DIAG_CLIP] / m,
+           "ratio_mean": s[DIAG_RATIO] / m}
+    if entropy:
+        out["entropy"] = s[DIAG_ENT] / m
+    out["value_mse"] = s[DIAG_E2] / m
+    var_e = s[DIAG_E2] / m - (s[DIAG_E] / m) ** 2
+    var_g = s[DIAG_G2] / m - (s[DIAG_G] / m) ** 2
+    out["explained_var"] = 1.0 - var_e / var_g if var_g > 0.0 else math.nan
+    return out
 
 
 # ------------------------------------------------------------- DP orchestration
