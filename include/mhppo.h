@@ -437,6 +437,33 @@ int mhppo_ppo_diag(const mhppo_mlp *actor, const mhppo_mlp *critic, const float 
                    const void *act, const float *logp_old, const float *ret, double *sums,
                    void *work, void *stream);
 
+/* ---- GAE(lambda) targets (csrc/mlp_gae.hip; opt-in, beyond the reference, which trains on the
+ * Monte-Carlo reward-to-go of mhppo_returns_scan_tm, futur_rewards :658-684) ---- */
+
+/* lambda-return targets over time-major records.  obs_tm float32 [T, B, n_in], rew_tm float64 [T, B],
+ * pos int64 [B] / bucket int8 [B] as mhppo_bucket_plan writes them (record b is used iff pos[b] >= 0;
+ * its critic is critic[bucket[b]]); pos == NULL: every record is used, with critic0 (critic1 and
+ * bucket may then be NULL).  ret_tm float32 [T, B] is written for every record (0 where pos[b] < 0);
+ * value_tm float32 [T, B] or NULL receives the critic outputs the scan used (0 where unused).
+ * V_t of a record is bit for bit what mhppo_mlp_forward returns for that row and critic (kind 0);
+ * the recurrence per record runs in float64, in this operation order (no contraction):
+ *   nv = 0; A = 0; c = gamma * lambda
+ *   for t = T-1 .. 0:  v = (double)V_t;  d = (rew[t] + gamma * nv) - v;  A = d + c * A;
+ *                      ret[t] = (float)(A + v);  nv = v
+ * i.e. ret = GAE advantage + V_old, without a bootstrap past step T-1 (the episode's time limit is
+ * terminal, as in the reward-to-go; lambda = 1 gives the reward-to-go up to float64 rounding).
+ * The train kernels form A = ret - V themselves, so these targets need no other change.
+ * A wave walks t backwards for 32 consecutive records (up to 1024 such tiles: one wave per tile and
+ * critic, the same operations per record); no atomics, nothing depends on the grid:
+ * the same call gives the same bits on any stream, and so does the batch split at a multiple of
+ * 32 records.  Observation rows of unused records are read but cannot influence another record.
+ * B == 0 launches nothing.  MHPPO_EINVAL: a NULL required pointer, T < 1, B < 0, a critic of kind
+ * != 0, n_in outside 1..64, two critics of different n_in, bucket == NULL with pos != NULL, gamma
+ * or lambda outside [0, 1] or NaN. */
+int mhppo_gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm,
+                 const double *rew_tm, const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T,
+                 double gamma, double lambda, float *ret_tm, float *value_tm, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

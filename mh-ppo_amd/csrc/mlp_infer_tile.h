@@ -143,6 +143,47 @@ __device__ __forceinline__ void stage_x(float *xs, const Img &g, const XStage &s
     }
   }
 }
+// stage_x in two halves, for a tile prefetched behind another tile's MFMA chain (mlp_gae.hip):
+// stage_x_issue starts the loads of the lane's first eight elements (every element of a tile of up
+// to 16 inputs) into registers, stage_x_land stores them to xs and stages what is left as stage_x
+// does.  src = X + r0 * n_in, the tile's first element.
+__device__ __forceinline__ void stage_x_issue(float (&pre)[8], const float *__restrict__ src, int nr, int n_in,
+                                              int lane) {
+  const int n = nr * n_in;
+#pragma unroll
+  for (int q = 0; q < 8; q++) {
+    const int e = lane + 64 * q;
+    pre[q] = e < n ? src[e] : 0.0f;
+  }
+}
+__device__ __forceinline__ void stage_x_land(float *xs, const Img &g, const XStage &s, const float (&pre)[8],
+                                             const float *__restrict__ src, int nr, int n_in, int lane) {
+  const int n = nr * n_in, tot = 32 * n_in;
+  int row = s.row0, col = s.col0;
+  float v[8];
+#pragma unroll
+  for (int q = 0; q < 8; q++) v[q] = pre[q];
+#pragma unroll 1
+  for (int e0 = lane;;) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      if (e0 + 64 * q < tot) xs[row * g.S1 + col] = v[q];
+      row += s.st_row;
+      col += s.st_col;
+      if (col >= n_in) {
+        col -= n_in;
+        row++;
+      }
+    }
+    e0 += 8 * 64;
+    if (e0 >= tot) break;
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      const int e = e0 + 64 * q;
+      v[q] = e < n ? src[e] : 0.0f;
+    }
+  }
+}
 // zero the padding columns of a staged input tile (once: stage_x never writes them)
 __device__ __forceinline__ void zero_x_pad(float *xs, const Img &g, int n_in, int lane) {
   const int pad = g.S1 - n_in;

@@ -100,6 +100,7 @@ _SIGS = {
     "mhppo_mlp_forward": (I32, [ctypes.POINTER(Mlp), P, I64, P, P]),
     "mhppo_ppo_diag_work_bytes": (I64, [I64]),
     "mhppo_ppo_diag": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, I64, P, P, P, P, P, P]),
+    "mhppo_gae_tm": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, P, I64, I32, F64, F64, P, P, P]),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }
@@ -141,6 +142,13 @@ def check(rc):
         cls = MhppoNaNError if rc == ENAN else MhppoError
         raise cls(f"libmhppo error {rc}: {lib().mhppo_last_error().decode()}")
     return rc
+
+
+def gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm, value_tm, stream):
+    """mhppo_gae_tm, checked: the one place the GAE entry point is called from (mhppo.rollout
+    .gae_targets_tm), so a run with the knob off can be shown never to reach it."""
+    return check(lib().mhppo_gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm, value_tm,
+                                    stream))
 
 
 def ptr(t):

@@ -50,6 +50,8 @@ class Env_rollout:
         self.seed = 0
         self.iteration = 0
         self.fix_bucket = False  # opt-in bug fix (Algo_PPO.fix_bucket)
+        # opt-in GAE(lambda) targets (Algo_PPO.gae_lambda): (critic_cross, critic_wait, gamma, lam)
+        self.gae = None
         self.env.reset(want_obs=False)  # the reference's __init__ resets the env (:107)
         self.batch = None
         self.cross = self.wait = self.choice = None
@@ -78,7 +80,7 @@ class Env_rollout:
         # NaN policy outputs raise, as torch.distributions does in the reference: the status word
         # comes back with the bucket sizes (the iteration's one host sync before the update)
         self.cross, self.wait, self.choice = bucket_segments(self.batch, fix_bucket=self.fix_bucket,
-                                                             status=self.gpu.status)
+                                                             status=self.gpu.status, gae=self.gae)
         return self.batch
 
     # reference-named views of the collected batch
@@ -210,8 +212,24 @@ class Algo_PPO:
         # every diagnostics_every-th iteration; off: the iteration runs exactly the code it always did
         self.diagnostics = False
         self.diagnostics_every = 1
+        # GAE(lambda) targets for the cross and wait heads (beyond the reference, which trains on the
+        # Monte-Carlo reward-to-go): None = off, the iteration runs exactly the code it always did;
+        # a value in [0, 1] makes the buckets' `ret` the lambda-returns A_t + V_old(s_t) under the
+        # pre-update critics (mhppo.rollout.gae_targets_tm), so the train kernels' A = ret - V is the
+        # GAE advantage in epoch 0 and the critics regress on the lambda-returns.  1.0 is the
+        # reward-to-go again (to float64 rounding).  The choice head keeps its episodic-min target.
+        # Nothing of it is checkpointed; the diagnostics' explained variance and value MSE are then
+        # relative to the lambda-returns (they read the buckets' `ret`).
+        self.gae_lambda = None
         for k, v in hyperparameters.items():
             setattr(self, k, v)
+        if self.gae_lambda is not None:
+            lam = float(self.gae_lambda)
+            if not 0.0 <= lam <= 1.0:  # (NaN fails both comparisons)
+                raise ValueError(f"gae_lambda must be None or in [0, 1], not {self.gae_lambda!r}")
+            if not 0.0 <= float(self.gamma) <= 1.0:
+                raise ValueError(f"gae_lambda needs gamma in [0, 1], not {self.gamma!r}")
+            self.gae_lambda = lam
 
     def update(self):
         """10 epochs of cross+wait, then 10 epochs of choice (:868-882) on the collected batch,
@@ -281,6 +299,9 @@ class Algo_PPO:
         replay (parity tests): one (forced_choice, eps_tape) pair per iteration, the
         recorded Categorical and MVN draws replayed instead of Philox noise."""
         self.rollout.fix_bucket = self.fix_bucket
+        lam = getattr(self, "gae_lambda", None)
+        # the critics are read when the buckets are built, before the iteration's update
+        self.rollout.gae = None if lam is None else (self.critic_net_cross, self.critic_net_wait, self.gamma, lam)
         for ep in range(nb_loop):
             self.rollout.reset()
             fc, et = replay[ep] if replay is not None else (None, None)

@@ -325,6 +325,68 @@ def returns_scan(rew, gamma=0.99):
     return out.reshape(rew.shape)
 
 
+def gae_targets_torch(rew_tm, v_tm, gamma, lam, out_dtype=torch.float32):
+    """lambda-return targets R_t = A_t + V_t over time-major records in float64 torch ops (any
+    device): the executable specification of mhppo_gae_tm's recurrence (include/mhppo.h, the
+    same operation order) and the CPU path.  rew_tm [T, ...] float64, v_tm [T, ...] -> float32
+    (out_dtype=torch.float64: the values before the cast).
+    A_t = sum_k (gamma lam)^k delta_{t+k}, delta_t = r_t + gamma V_{t+1} - V_t, V_T = 0: no
+    bootstrap past the last step (the episode's time limit is terminal, as in futur_rewards)."""
+    if rew_tm.shape != v_tm.shape:
+        raise ValueError("gae_targets_torch: rew_tm and v_tm differ in shape")
+    r, v = rew_tm.double(), v_tm.double()
+    out = torch.empty(r.shape, dtype=out_dtype, device=r.device)
+    c = float(gamma) * float(lam)
+    A = torch.zeros_like(r[0])
+    nv = torch.zeros_like(r[0])
+    for t in range(r.shape[0] - 1, -1, -1):
+        d = (r[t] + gamma * nv) - v[t]
+        A = d + c * A
+        out[t] = (A + v[t]).to(out_dtype)
+        nv = v[t]
+    return out
+
+
+def gae_targets_tm(obs_tm, rew_tm, critic0, critic1=None, pos=None, bucket=None, gamma=0.99, lam=0.95,
+                   want_value=False):
+    """mhppo_gae_tm: the critics' forward and the lambda-return scan over time-major records in one
+    launch.  obs_tm float32 [T, ..., n_in], rew_tm float64 [T, ...] (B records per step) on the
+    critics' GPU; pos int64 [B] / bucket int8 [B] as mhppo_bucket_plan writes them (record b is used
+    iff pos[b] >= 0, with critic0 / critic1 for bucket 0 / 1), or pos=None: every record, critic0.
+    Returns ret float32 shaped like rew_tm (0 for unused records), with want_value also the critic
+    outputs the scan used.  V is forward_rows' bit for bit; the recurrence is gae_targets_torch's."""
+    T = rew_tm.shape[0]
+    dev = rew_tm.device
+    B = rew_tm[0].numel()
+    r = rew_tm.reshape(T, B).contiguous()
+    x = obs_tm.reshape(T, B, obs_tm.shape[-1]).contiguous()
+    if x.dtype != torch.float32 or r.dtype != torch.float64 or x.device != dev or dev.type != "cuda":
+        raise ValueError("gae_targets_tm takes float32 observations and float64 rewards on one GPU")
+    if x.shape[2] != critic0.n_in:
+        raise ValueError(f"gae_targets_tm: observations of width {x.shape[2]} for a critic of {critic0.n_in} inputs")
+    if pos is not None:
+        if critic1 is None or bucket is None:
+            raise ValueError("gae_targets_tm: pos needs bucket and critic1")
+        if (pos.dtype != torch.int64 or bucket.dtype != torch.int8 or pos.numel() != B or bucket.numel() != B
+                or pos.device != dev or bucket.device != dev):
+            raise ValueError(f"gae_targets_tm: pos int64 [{B}] and bucket int8 [{B}] on the records' device")
+        pos, bucket = pos.contiguous(), bucket.contiguous()
+    else:
+        bucket = None
+    ret = torch.empty((T, B), dtype=torch.float32, device=dev)
+    val = torch.empty((T, B), dtype=torch.float32, device=dev) if want_value else None
+    d0, keep0 = critic0.mlp_desc()
+    d1, keep1 = critic1.mlp_desc() if critic1 is not None else (None, None)
+    if keep0.device != dev or (keep1 is not None and keep1.device != dev):
+        raise ValueError("gae_targets_tm: the critics must live on the records' device")
+    with torch.cuda.device(dev):
+        _lib.gae_tm(ctypes.byref(d0), ctypes.byref(d1) if d1 is not None else None, _lib.ptr(x), _lib.ptr(r),
+                    _lib.ptr(pos), _lib.ptr(bucket), B, T, float(gamma), float(lam), _lib.ptr(ret), _lib.ptr(val),
+                    _lib.stream_ptr(device=dev))
+    ret = ret.reshape(rew_tm.shape)
+    return (ret, val.reshape(rew_tm.shape)) if want_value else ret
+
+
 NAN_STATUS_MSG = {1: "Categorical probs of the choice actor, :409",
                   2: "MultivariateNormal loc of the continuous actors, :451"}
 
@@ -338,7 +400,7 @@ def raise_if_nan_status(st):
         raise _lib.MhppoNaNError(f"NaN policy output sampled ({what}): the reference raises ValueError here")
 
 
-def bucket_segments(batch, fix_bucket=False, status=None):
+def bucket_segments(batch, fix_bucket=False, status=None, gae=None):
     """Split (env, slot) episode segments into the reference's cross/wait/choice batches.
     fix_bucket=True (opt-in bug fix) buckets car i by ITS closest
     pedestrian's decision action_d[i*P + closest_i] instead of the flat action_d[i].
@@ -358,10 +420,16 @@ def bucket_segments(batch, fix_bucket=False, status=None):
     also runs on CUDA tensors: it is the native pass's reference.  The native path adds
     choice["rew_sums"]: float64 [3] on the device, the sums over the cross rows' / the wait
     rows' float32 rewards and the choice batch's `ret` (Algo_PPO.train's reward curves).
+
+    gae = (critic_cross, critic_wait, gamma, lam) (opt-in, Algo_PPO(gae_lambda=...)): the cross /
+    wait buckets' `ret` are the GAE(lam) lambda-returns A_t + V_t under those critics instead of the
+    reward-to-go (gae_targets_tm on the GPU: one launch with the plan's pos / bucket, queued before
+    the host read, in place of the returns scan; gae_targets_torch on the torch path).  The choice
+    batch keeps its episodic-min target: it is a one-step decision.
     """
     if batch.a_d.device.type == "cuda":
-        return bucket_segments_native(batch, fix_bucket, status)
-    return bucket_segments_torch(batch, fix_bucket, status)
+        return bucket_segments_native(batch, fix_bucket, status, gae=gae)
+    return bucket_segments_torch(batch, fix_bucket, status, gae=gae)
 
 
 def bucket_plan(batch, fix_bucket=False, status=None):
@@ -395,20 +463,27 @@ def bucket_plan(batch, fix_bucket=False, status=None):
     return out
 
 
-def bucket_segments_native(batch, fix_bucket=False, status=None):
+def bucket_segments_native(batch, fix_bucket=False, status=None, gae=None):
     """bucket_segments on the GPU: the returns scan and mhppo_bucket_plan, then ONE scatter of both
     buckets into a shared buffer of NS + 3 segments that also folds the cross / wait reward sums
     (mhppo_bucket_scatter_sums).  The one host read comes right after the plan, before the scatter
     is queued (it needs no sizes): the update's host-side preparation then runs while the scatter
     does, instead of in an idle gap before the first critic launch.  (The returns stay their own
     pass: computed inside the scatter, by one wave per 64-segment block, the iteration was 1.1 ms
-    slower at config 3)"""
+    slower at config 3)  With gae the returns scan is replaced by
+    mhppo_gae_tm, queued after the plan (it takes the plan's pos / bucket) and before the read."""
     N, S, P, T = batch.N, batch.S, batch.P, batch.T
     NS = N * S
     dev = batch.a_d.device
     L = _lib.lib()
-    ret_tm = returns_scan_tm(batch.rew_tm)  # [T, N, S]
-    plan = bucket_plan(batch, fix_bucket, status)
+    if gae is None:
+        ret_tm = returns_scan_tm(batch.rew_tm)  # [T, N, S]
+        plan = bucket_plan(batch, fix_bucket, status)
+    else:
+        critic_cross, critic_wait, gamma, lam = gae
+        plan = bucket_plan(batch, fix_bucket, status)
+        ret_tm = gae_targets_tm(batch.obs_c_tm, batch.rew_tm, critic_cross, critic_wait, plan["pos"], plan["bucket"],
+                                gamma, lam)
     info = plan["info"]
     n = NS + 3
     both = dict(obs=torch.empty(n * T, NF_C, dtype=torch.float32, device=dev),
@@ -442,11 +517,12 @@ def bucket_segments_native(batch, fix_bucket=False, status=None):
     return cross_r, wait_r, choice
 
 
-def bucket_segments_torch(batch, fix_bucket=False, status=None, plan_out=None):
+def bucket_segments_torch(batch, fix_bucket=False, status=None, plan_out=None, gae=None):
     """bucket_segments with torch ops (any device): the CPU path, and the reference the native
     plan is tested against.  The segment lists are built with nonzero_static at NS rows, so
     everything is queued before the one host read.  plan_out: a dict that receives the scatter's
-    `pos` (per record with the compact layout) and the `wait` segment mask (tests)."""
+    `pos` (per record with the compact layout) and the `wait` segment mask (tests).  With gae the
+    buckets' `ret` come from gae_targets_torch with V = critic(obs) (torch's forward) per bucket."""
     N, S, P, T = batch.N, batch.S, batch.P, batch.T
     a_flat = batch.a_d.reshape(N, S * P)
     if fix_bucket:
@@ -468,7 +544,10 @@ def bucket_segments_torch(batch, fix_bucket=False, status=None, plan_out=None):
     # bucketing's peak memory): cross segments from slot 0, wait segments from slot w0 = the cross
     # count rounded up to a multiple of 4, computed on the device, so the wait bucket's observation
     # rows start 16-byte aligned at any T (the train kernels' LDS-DMA rows; 4 T 52 B = 16 T 13 B).
-    ret = returns_scan_tm(batch.rew_tm)  # [T, N, S]
+    if gae is None:
+        ret = returns_scan_tm(batch.rew_tm)  # [T, N, S]
+    else:  # the buckets' ret are computed from the scattered rows below
+        ret = torch.zeros(batch.rew_tm.shape, dtype=torch.float32, device=batch.rew_tm.device)
     cc, cw = torch.cumsum(cross, 0), torch.cumsum(wait, 0)
     w0 = torch.div(cc[-1] + 3, 4, rounding_mode="floor") * 4
     pos = torch.where(cross, cc - 1, torch.where(wait, w0 + cw - 1, -1))
@@ -507,6 +586,12 @@ def bucket_segments_torch(batch, fix_bucket=False, status=None, plan_out=None):
     cross_r = {k: both[k][:n_cross * T] for k in ("obs", "act", "logp", "ret", "rew")}
     wait_r = {k: both[k][c0 * T:(c0 + n_wait) * T] for k in ("obs", "act", "logp", "ret", "rew")}
     cross_r["n_seg"], wait_r["n_seg"] = n_cross, n_wait
+    if gae is not None:
+        for b, critic in ((cross_r, gae[0]), (wait_r, gae[1])):
+            n = b["ret"].numel() // T
+            with torch.no_grad():
+                v = critic(b["obs"]).reshape(n, T)
+            b["ret"] = gae_targets_torch(b["rew"].reshape(n, T).t(), v.t(), gae[2], gae[3]).t().reshape(-1)
     choice = {k: v[:n_all] for k, v in choice.items()}
     choice["n_seg"] = n_all
     choice["counts"] = counts  # float64 [2] on the device: (act == 0).sum(), (act == 1).sum()
