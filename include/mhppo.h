@@ -176,6 +176,7 @@ typedef struct mhppo_rollout_bufs {
  * kernel (bit-identical).  Those kernels are compiled into the test build only
  * (tests/lib/libmhppo_test.so, -DMHPPO_TEST_KERNELS); the shipped library returns MHPPO_EINVAL. */
 #define MHPPO_ROLLOUT_VALU_POLICY 1
+#define MHPPO_ROLLOUT_VALU_UNSORTED 2 /* with _VALU_POLICY: the unsorted one-lane-per-row kernel (test build only) */
 
 int mhppo_choice_dim(const mhppo_env *env);
 

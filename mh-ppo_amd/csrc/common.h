@@ -1,4 +1,5 @@
-// common.h — error reporting shared by the libmhppo.so translation units.
+// common.h — what the libmhppo.so translation units share on the host side: error reporting, the
+// device guard of an ABI call and the per-device scratch buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -27,6 +28,13 @@ struct DeviceGuard {
 };
 // per-device tables (workspaces, CU counts) hold this many devices
 constexpr int MAX_DEVICES = 16;
+
+// n doubles of device scratch on the current device, or nullptr (allocation failed, or a device
+// number >= MAX_DEVICES).  ONE buffer per device, grown on demand (growing frees the old one) and
+// shared by mhppo_rollout_begin's block counts and the loss entry points' block partials: every
+// use is stream-ordered, and a call's contents mean nothing to the next.  (Hidden: the library's
+// dynamic symbol list stays what it was.)
+__attribute__((visibility("hidden"))) double *scratch(size_t n);
 }  // namespace mhppo
 using mhppo::set_error;
 

@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(ITPB) __attribute__((amdgpu_waves_per_eu(2)))
 }
 
 // sums[k] = the block partials of term k: a fixed strided subset per thread, then a fixed tree
-// (rollout.hip k_sum_partials' order; writes instead of adding)
+// (ppo_loss.hip k_sum_partials' order; writes instead of adding)
 __global__ void __launch_bounds__(ITPB) k_diag_fold(const double *__restrict__ partials, int nblocks, double *sums) {
   __shared__ double sh[ITPB];
   const int k = blockIdx.x;

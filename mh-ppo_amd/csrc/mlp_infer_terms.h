@@ -49,7 +49,7 @@ MHPPO_HD inline double choice_entropy(float n0, float n1) {
 
 // The actor's terms of one row (t: double [MHPPO_DIAG_N], entries DSUM .. ENT written).
 // d = logp_new - logp_old is exact in float64 (a difference of two floats); the clip decision is
-// the train kernels' (rollout_dev.h surr_and_grad_fd: d against float64 ln 0.8 / ln 1.2).
+// the train kernels' (ppo_math.h surr_and_grad_fd: d against float64 ln 0.8 / ln 1.2).
 MHPPO_HD inline double actor_terms(float logp_new, float logp_old, double ent, double *t) {
   const double d = (double)logp_new - (double)logp_old;
   t[MHPPO_DIAG_DSUM] = d;

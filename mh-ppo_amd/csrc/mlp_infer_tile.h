@@ -1,24 +1,20 @@
 // mlp_infer_tile.h — one 32-row tile of a Model_PPO net (n_in <= 64 -> 32 -> 64 -> 32 -> 1 or 2) on
 // f32 MFMA, forward only (device; mlp_infer.hip).
 //
-// The scheme of the rollout's 13 -> 1 actor tile (rollout.hip pol::actor_tile), generalised to a
-// run-time input width and one or two outputs: rows on the lanes (lane j of both halves = tile row
-// j), v_mfma_f32_32x32x2_f32 with the weights as the A operand and the inputs as B, so C register r
-// of lane half kh holds tile row (r & 3) + 8 (r >> 2) + 4 kh of the layer's output.  The weight
-// rows of layers 1-3 are staged in LDS permuted so that this tile row is neuron 2 r + kh: k-step
-// s of the next layer then consumes inputs 2 s, 2 s + 1 straight from register s, and every chain
-// runs in ascending input order.  The f32 MFMA is bit for bit a k-ordered fmaf chain
-// (one rounding per product), so each output equals mlp_forward's (rollout_dev.h): ascending-k
-// fmaf from 0, the bias added last.  Layer 1 runs ceil(n_in / 2) k-steps; an odd n_in is padded
-// with a zero weight column and a zero input column (fmaf(0, 0, acc) == acc).
+// The scheme of the rollout's 13 -> 1 actor tile (rollout_policy.h pol::actor_tile), generalised to
+// a run-time input width and one or two outputs, on the same tile primitives and LDS row
+// permutation (mfma_tile.h): C register r of lane half kh holds neuron 2 r + kh of the layer's
+// output, so every chain runs in ascending input order.  The f32 MFMA is bit for bit a k-ordered
+// fmaf chain (one rounding per product), so each output equals mlp_forward's (rollout_dev.h):
+// ascending-k fmaf from 0, the bias added last.  Layer 1 runs ceil(n_in / 2) k-steps; an odd n_in
+// is padded with a zero weight column and a zero input column (fmaf(0, 0, acc) == acc).
 #pragma once
+#include "mfma_tile.h"
 #include "rollout_dev.h"
 
 namespace mhppo {
 namespace infer {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int S2 = 33, S3 = 65;  // odd LDS row strides of W2 / W3: conflict-free operand reads
+using namespace mfma_tile;  // f32x16, mfma, zero16, bias_relu, row_of_neuron, S2, S3
 
 // LDS image of one net (floats).  S1: row stride of W1 and of a staged input tile: odd, and wide
 // enough for the 2 ceil(n_in / 2) columns layer 1 reads.  The bias arrays start at multiples of 4
@@ -41,33 +37,6 @@ __host__ __device__ inline Img img_layout(int n_in, int n_out) {
   return g;
 }
 __host__ __device__ inline int xtile_floats(const Img &g) { return (32 * g.S1 + 3) / 4 * 4; }
-
-__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; i++) z[i] = 0.0f;
-  return z;
-}
-// LDS row holding neuron n (0..31): the inverse of row(r, kh) -> neuron 2 r + kh above
-__device__ __forceinline__ int row_of_neuron(int n) {
-  const int m = n >> 1;
-  return (m & 3) + 8 * (m >> 2) + 4 * (n & 1);
-}
-// v[r] = relu(v[r] + b[row(r)]) with the oracle's relu (x < 0 ? 0 : x)
-__device__ __forceinline__ void bias_relu(f32x16 &v, const float *b, int kh) {
-  const float4 *b4 = reinterpret_cast<const float4 *>(b);
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const float4 c = b4[2 * q + kh];
-    v[4 * q + 0] = relu(v[4 * q + 0] + c.x);
-    v[4 * q + 1] = relu(v[4 * q + 1] + c.y);
-    v[4 * q + 2] = relu(v[4 * q + 2] + c.z);
-    v[4 * q + 3] = relu(v[4 * q + 3] + c.w);
-  }
-}
 
 // One torch-packed net (W1 b1 W2 b2 W3 b3 W4 b4) into its LDS image: the rows of W1 / W2 / W3 and
 // the entries of b1 / b2 / b3 at the permuted row of their neuron, W1's padding columns zeroed.
@@ -193,6 +162,9 @@ __device__ __forceinline__ void zero_x_pad(float *xs, const Img &g, int n_in, in
 
 // One 32-row tile through one net (Wl: its LDS image; xs: the wave's staged inputs): z[o] = output o
 // of tile row j before the head's finish, in every lane of both halves.
+// Layers 2-4 are the chain of pol::actor_tile (rollout_policy.h) with this image's run-time offsets:
+// change the two together.  (No form of one shared function left both these kernels' instruction
+// streams and k_policy_mfma's as they were: profiles/rollout_split/kernels.txt.)
 template <int NOUT>
 __device__ __forceinline__ void tile_forward(const float *Wl, const Img &g, const float *xs, int j, int kh,
                                              float (&z)[NOUT]) {

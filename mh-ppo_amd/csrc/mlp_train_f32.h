@@ -40,7 +40,7 @@
 #include <math.h>
 
 #include "mlp_tile.h"
-#include "rollout_dev.h"  // surr_and_grad, the MVN constants, MHPPO_MARK
+#include "rollout_dev.h"  // surr_and_grad, the MVN constants (ppo_math.h), MHPPO_MARK
 
 using namespace mhppo;
 

@@ -38,7 +38,7 @@
 
 #include "mlp_tile.h"
 #include "mlp_x3_prims.h"
-#include "rollout_dev.h"  // surr_and_grad, surr_and_grad_fd, the MVN constants, MHPPO_MARK
+#include "rollout_dev.h"  // surr_and_grad, surr_and_grad_fd, the MVN constants (ppo_math.h), MHPPO_MARK
 
 using namespace mhppo;
 

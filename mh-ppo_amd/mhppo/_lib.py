@@ -116,6 +116,9 @@ class MhppoNaNError(MhppoError, ValueError):
     """MHPPO_ENAN: a NaN policy output was sampled (the reference raises ValueError there)."""
 
 ENAN = -4
+# mhppo_rollout_bufs.flags (include/mhppo.h; the VALU kernels are in the test build only)
+MHPPO_ROLLOUT_VALU_POLICY = 1
+MHPPO_ROLLOUT_VALU_UNSORTED = 2
 
 
 def lib():

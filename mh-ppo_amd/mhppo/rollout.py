@@ -126,7 +126,8 @@ class RolloutGPU:
         # policy step on the VALU reference kernels instead of the MFMA one (bit-identical; tests, with
         # the test build of the library: MHPPO_LIB=tests/lib/libmhppo_test.so); "unsorted": the
         # one-lane-per-row kernel
-        b.flags = {False: 0, True: 1, "unsorted": 3}[valu_policy]  # MHPPO_ROLLOUT_VALU_POLICY
+        b.flags = {False: 0, True: _lib.MHPPO_ROLLOUT_VALU_POLICY,
+                   "unsorted": _lib.MHPPO_ROLLOUT_VALU_POLICY | _lib.MHPPO_ROLLOUT_VALU_UNSORTED}[valu_policy]
         b.parts = self.parts
         self._bufs = b
         # captured one-chain step loops, keyed by what their launches bake in (collect)

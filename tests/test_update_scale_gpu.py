@@ -108,7 +108,7 @@ def test_actor_clip_at_bench_scale_vs_float64_autograd(exact):
     well past the clip bounds 0.8 / 1.2 (Coop-MH-PPO-scalable.py:803-806): the kernel's gradient
     against a float64 autograd with the reference's float64 ratio, at the 1e-4 max|g| bar.
     The kernel takes the clip branch from the float64 difference lp - logp_old
-    (rollout_dev.h surr_and_grad_fd); the test also counts, on torch's float32 lp of the same
+    (ppo_math.h surr_and_grad_fd); the test also counts, on torch's float32 lp of the same
     weights, the rows whose branch a float32 ratio expf(lp - logp_old) would flip against the
     float64 one, and the rows whose branch float32 lp itself moves against float64 lp (present in
     the reference too, whose actor is float32) — printed, recorded in DESIGN.md §5."""

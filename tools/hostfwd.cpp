@@ -54,7 +54,7 @@ int hf_diag_rows(int akind, int n_in, const float *Wa, float mean, float std, co
   return 0;
 }
 
-// MVN(mu, 0.5).log_prob(act) as the rollout records it (rollout_dev.h mvn_logp)
+// MVN(mu, 0.5).log_prob(act) as the rollout records it (ppo_math.h mvn_logp)
 void hf_mvn_logp(const float *act, const float *mu, int64_t M, float *out) {
   for (int64_t r = 0; r < M; r++) out[r] = mvn_logp(act[r], mu[r]);
 }
