@@ -199,7 +199,9 @@ typedef struct mhppo_eval_bufs {
 /* Step t of an evaluation episode in every env (t = 0 right after mhppo_env_reset):
  * choice argmax when a decision is due (t = 0 or the re-decision test fired), per car
  * a = min over pedestrians of the head's mean action (left-lane pedestrians: clamped
- * speed-limit tracking), capped by (10 - V)/dt; lights = 2 a_d[flat i] - 1; env step. */
+ * speed-limit tracking), capped by (10 - V)/dt; lights = 2 a_d[flat i] - 1; env step.
+ * A NULL obs_hist, acts, rews_c, rews_d or waiting skips that history's stores (the streaming
+ * statistics below keep none); saved [T, N] stays required: it is the step's done scratch. */
 int mhppo_eval_step(mhppo_env *env, const mhppo_mlp *actor_cross, const mhppo_mlp *actor_wait,
                     const mhppo_mlp *actor_choice, int t, mhppo_eval_bufs *bufs, void *stream);
 
@@ -464,6 +466,73 @@ int mhppo_ppo_diag(const mhppo_mlp *actor, const mhppo_mlp *critic, const float 
 int mhppo_gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm,
                  const double *rew_tm, const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T,
                  double gamma, double lambda, float *ret_tm, float *value_tm, void *stream);
+
+/* ---- streaming evaluation statistics (csrc/eval_stats.hip; opt-in, beyond the reference, whose
+ * get_average (Coop-MH-PPO-scalable.py:1550-1675) reads whole trajectories back) ---- */
+
+/* What get_average's dict needs, reduced on the device to MHPPO_EVS_N float64 sums without keeping
+ * a trajectory: counts (integer-valued float64, exact below 2^53) and the first and second moments
+ * of the terms get_average hands to its reductions, each term computed as get_average computes it
+ * (float32 comparisons and differences; 0.3-step sums in float64; csrc/eval_stats_terms.h) and
+ * widened to float64 before it is added.  The moments are plain sums, about no pivot: the terms
+ * are speeds, accelerations and times of a few tens at most, so the variance's cancellation
+ * S2 - S^2 / n costs ~n 2^-53 relative to the mean square, far below float32.  The sums add across
+ * ranks.  mhppo.stats.stats_from_sums turns them into the dict.
+ * Episodes are the true ones (one per env from row 0 to row T - 1), not get_average's maximal runs of
+ * equal crosswalk width; the two agree whenever consecutive episodes differ in width. */
+#define MHPPO_EVS_ROWS       0  /* rows                                                   */
+#define MHPPO_EVS_V0         1  /* sum over rows of car 0's speed                         */
+#define MHPPO_EVS_V0_SQ      2  /*   ... squared                                          */
+#define MHPPO_EVS_ABSA0      3  /* sum over rows of |car 0's acceleration|                */
+#define MHPPO_EVS_A0         4  /* sum over rows of car 0's acceleration                  */
+#define MHPPO_EVS_A0_SQ      5  /*   ... squared                                          */
+#define MHPPO_EVS_ABSVP0     6  /* sum over rows of |pedestrian 0's speed|                */
+#define MHPPO_EVS_ABSVP0_SQ  7  /*   ... squared                                          */
+#define MHPPO_EVS_EPISODES   8  /* episodes closed                                        */
+#define MHPPO_EVS_N_PED      9  /* (episode, pedestrian) entries                          */
+#define MHPPO_EVS_PEDT      10  /* sum of the pedestrians' pass times (float32)           */
+#define MHPPO_EVS_PEDT_SQ   11
+#define MHPPO_EVS_WAIT      12  /* sum of the waiting times (float64), n = N_PED          */
+#define MHPPO_EVS_WAIT_SQ   13
+#define MHPPO_EVS_N_CAR     14  /* (episode, car) entries                                 */
+#define MHPPO_EVS_CART      15  /* sum of the cars' pass times (float32)                  */
+#define MHPPO_EVS_CART_SQ   16
+#define MHPPO_EVS_FC        17  /* sum of fci - fcn over peds and cars, n = N_PED + N_CAR */
+#define MHPPO_EVS_IC        18  /* sum of max fci - max fcn per episode, n = EPISODES     */
+#define MHPPO_EVS_N_YSPEED  19  /* pairs of episodes whose car yields (light 1 at row 1)  */
+#define MHPPO_EVS_YSPEED    20  /* sum of that car's speed at the pair's first row        */
+#define MHPPO_EVS_YSPEED_SQ 21
+#define MHPPO_EVS_N_YTIME   22  /* those pairs at which the car passes the crosswalk      */
+#define MHPPO_EVS_YTIME     23  /* sum of their times k * 0.3 (float32)                   */
+#define MHPPO_EVS_YTIME_SQ  24
+#define MHPPO_EVS_YIELD     25  /* car decisions (light at row T - 2) equal to 1          */
+#define MHPPO_EVS_GO        26  /*   ... equal to -1                                      */
+#define MHPPO_EVS_N_CS      27  /* could_stop entries (light at row 1 < 0)                */
+#define MHPPO_EVS_CS        28  /*   ... that could stop                                  */
+#define MHPPO_EVS_SC_YY     29  /* two cars: both yield                                   */
+#define MHPPO_EVS_SC_GG     30  /*   both go                                              */
+#define MHPPO_EVS_SC_GY     31  /*   car 0 goes, car 1 yields                             */
+#define MHPPO_EVS_SC_YG     32  /*   car 0 yields, car 1 goes                             */
+#define MHPPO_EVS_N         33
+
+/* Bytes of the caller-owned device state (8-byte aligned) for this env's N, S, P:
+ * N * (8 MHPPO_EVS_N + 4 (1 + 2 P + 5 nb_car) + 4 (2 P + nb_car)), i.e. per env the float64
+ * accumulators, the previous row's fields the pair tests need and the episode's counters.
+ * MHPPO_EINVAL (negative) for the 4cars / 4cars2 layouts, which get_average is not defined for. */
+int64_t mhppo_eval_stats_bytes(const mhppo_env *env);
+/* Zero the state (accumulators and carry). */
+int mhppo_eval_stats_begin(mhppo_env *env, void *state, void *stream);
+/* Consume row t (0 <= t < T) of the current episode of every env: obs float32 [N, obs_dim], the
+ * pre-step observation mhppo_eval_step copies into obs_hist[t] (bufs->obs before the step), or a
+ * row of a recorded trajectory.  t == 0 opens an episode, t >= 1 closes the pair (t - 1, t),
+ * t == T - 1 closes the episode into the env's accumulators.  Rows of one episode must arrive in
+ * order.  One lane per env; a block stages its envs' rows through LDS in one coalesced copy.
+ * MHPPO_EINVAL: T < 2, t outside [0, T), a NULL pointer, an unsupported layout. */
+int mhppo_eval_stats_row(mhppo_env *env, const float *obs, int t, int T, void *state, void *stream);
+/* sums float64 [MHPPO_EVS_N] (device) is WRITTEN with the per-env accumulators folded over the envs
+ * in a fixed order (one block per sum, a fixed env-to-thread assignment and a fixed tree: no atomics,
+ * the same call gives the same bits on any stream).  The state is left as it is: more rows may follow. */
+int mhppo_eval_stats_fold(mhppo_env *env, const void *state, double *sums, void *stream);
 
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);

@@ -431,6 +431,9 @@ int mhppo_rollout_check(mhppo_rollout_bufs *bufs, void *stream) {
 int mhppo_eval_step(mhppo_env *env, const mhppo_mlp *actor_cross, const mhppo_mlp *actor_wait,
                     const mhppo_mlp *actor_choice, int t, mhppo_eval_bufs *bufs, void *stream) {
   if (!env || !actor_cross || !actor_wait || !actor_choice || !bufs) return set_error(MHPPO_EINVAL, "null argument");
+  // the histories (obs_hist, acts, rews_c, rews_d, waiting) may be NULL: their stores are skipped
+  if (!bufs->obs || !bufs->a_d || !bufs->trig || !bufs->ep_min || !bufs->saved)
+    return set_error(MHPPO_EINVAL, "eval bufs: obs, a_d, trig, ep_min and saved are required");
   const Cfg &c = env_cfg(env);
   if (actor_cross->n_in != NF_C || actor_wait->n_in != NF_C || actor_cross->n_out != 1 || actor_wait->n_out != 1)
     return set_error(MHPPO_EINVAL, "continuous actors must be 13 -> 1");

@@ -270,8 +270,10 @@ __global__ void __launch_bounds__(TPB) k_eval_step(Cfg c, Bufs eb, mhppo_mlp mc,
       }
   }
   const size_t te = (size_t)t * N + e;
-  float *oh = E.obs_hist + te * L.obs_dim;
-  for (int k = 0; k < L.obs_dim; k++) oh[k] = o[k];
+  if (E.obs_hist) {  // a NULL history skips its stores (include/mhppo.h mhppo_eval_step)
+    float *oh = E.obs_hist + te * L.obs_dim;
+    for (int k = 0; k < L.obs_dim; k++) oh[k] = o[k];
+  }
   double act[2 * MAXS], rw[MAXS], rl[MAXS];
   for (int i = 0; i < S; i++) {
     double a = c.b10;  // np.array(car_b[1,0]) (:193)
@@ -296,14 +298,14 @@ __global__ void __launch_bounds__(TPB) k_eval_step(Cfg c, Bufs eb, mhppo_mlp mc,
       if (lim < a) a = lim;
     }
     act[i] = a;
-    E.acts[te * S + i] = (float)a;
+    if (E.acts) E.acts[te * S + i] = (float)a;
   }
   for (int i = 0; i < S; i++) act[S + i] = (double)(2 * ad[i] - 1);  // action_d_light: flat index (:188, :210)
   const float prev1 = o[L.env_off + 1];
   env_step_one<V>(c, eb, e, act, E.obs, rw, rl, E.saved + (size_t)t * N);  // writes done into saved[t][e]
   const uint8_t done = E.saved[te];
   for (int i = 0; i < S; i++) {
-    E.rews_c[te * S + i] = (float)rw[i];
+    if (E.rews_c) E.rews_c[te * S + i] = (float)rw[i];
     double m = epm[i], x = rl[i];
     epm[i] = (m != m) ? m : ((x != x) ? x : (x < m ? x : m));  // np.minimum
   }
@@ -313,8 +315,10 @@ __global__ void __launch_bounds__(TPB) k_eval_step(Cfg c, Bufs eb, mhppo_mlp mc,
   E.saved[te] = saved;
   E.trig[e] = trig;
   if (saved) {  // (:224-229)
-    for (int i = 0; i < S; i++) E.rews_d[te * S + i] = (float)epm[i];
-    for (int p = 0; p < P; p++) E.waiting[te * P + p] = (float)eb.ped[sidx(P_NF * P, P_WT * P + p, e)];
+    if (E.rews_d)
+      for (int i = 0; i < S; i++) E.rews_d[te * S + i] = (float)epm[i];
+    if (E.waiting)
+      for (int p = 0; p < P; p++) E.waiting[te * P + p] = (float)eb.ped[sidx(P_NF * P, P_WT * P + p, e)];
   }
 }
 

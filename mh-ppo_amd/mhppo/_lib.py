@@ -101,6 +101,10 @@ _SIGS = {
     "mhppo_ppo_diag_work_bytes": (I64, [I64]),
     "mhppo_ppo_diag": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, I64, P, P, P, P, P, P]),
     "mhppo_gae_tm": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, P, I64, I32, F64, F64, P, P, P]),
+    "mhppo_eval_stats_bytes": (I64, [P]),
+    "mhppo_eval_stats_begin": (I32, [P, P, P]),
+    "mhppo_eval_stats_row": (I32, [P, P, I32, I32, P, P]),
+    "mhppo_eval_stats_fold": (I32, [P, P, P, P]),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }
@@ -152,6 +156,27 @@ def gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_
     .gae_targets_tm), so a run with the knob off can be shown never to reach it."""
     return check(lib().mhppo_gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm, value_tm,
                                     stream))
+
+
+# The streaming evaluation statistics' entry points, checked: the one place each is called from
+# (mhppo.rollout), so evaluate() can be shown never to reach them.
+def eval_stats_bytes(env):
+    n = lib().mhppo_eval_stats_bytes(env)
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def eval_stats_begin(env, state, stream):
+    return check(lib().mhppo_eval_stats_begin(env, state, stream))
+
+
+def eval_stats_row(env, obs, t, T, state, stream):
+    return check(lib().mhppo_eval_stats_row(env, obs, t, T, state, stream))
+
+
+def eval_stats_fold(env, state, sums, stream):
+    return check(lib().mhppo_eval_stats_fold(env, state, sums, stream))
 
 
 def ptr(t):

@@ -70,6 +70,13 @@ class Env_rollout:
         with torch.no_grad():
             return self.gpu.evaluate(actor_net_cross, actor_net_wait, actor_net_choice, nbr_episodes, choix=choix)
 
+    def iterations_stats(self, actor_net_cross, actor_net_wait, actor_net_choice, nbr_episodes, choix=False):
+        """iterations() reduced on the device to get_average's sums (RolloutGPU.evaluate_stats;
+        opt-in, beyond the reference): float64 [MHPPO_EVS_N] on the env's device, no trajectory."""
+        with torch.no_grad():
+            return self.gpu.evaluate_stats(actor_net_cross, actor_net_wait, actor_net_choice, nbr_episodes,
+                                           choix=choix)
+
     def iterations_rand(self, actor_net_cross, actor_net_wait, actor_net_choice, cov_mat=None, cov_mat_d=None,
                         batch_size=None, random_rate=0.0, forced_choice=None, eps_tape=None):
         """One episode in every env (:357-517); buckets the segments like :489-507."""
@@ -284,6 +291,21 @@ class Algo_PPO:
         self.rollout.reset()
         return self.rollout.iterations(self.actor_net_cross, self.actor_net_wait, self.actor_net_choice,
                                        nbr_episodes, choix=choix)
+
+    def evaluate_stats(self, nbr_episodes, choix=False):
+        """get_average(evaluate(nbr_episodes)[0]) without the trajectories (opt-in, beyond the
+        reference): the same reset, episodes and env draws as evaluate(), reduced on the device to
+        the statistics' sums (memory O(N) whatever nbr_episodes is), all-reduced once under data
+        parallelism, then mhppo.stats.stats_from_sums.  Same keys as get_average; float64 sums
+        where get_average reduces in float32.  Episodes are the true ones (N * nbr_episodes): under
+        choix=True, where every episode has crosswalk width 3, get_average sees one long run instead."""
+        from .stats import check_variant, stats_from_sums
+        check_variant(self.venv.variant)
+        self.rollout.reset()
+        sums = self.rollout.iterations_stats(self.actor_net_cross, self.actor_net_wait, self.actor_net_choice,
+                                             nbr_episodes, choix=choix)
+        ppo._allreduce_(sums)
+        return stats_from_sums(sums, self.venv.nb_car)
 
     def get_average(self, states):
         """The paper cell's evaluation statistics (get_average, :1550-1675; CO2 leg excluded)

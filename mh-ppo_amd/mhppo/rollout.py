@@ -75,6 +75,40 @@ def default_graph():
     return {"0": 0, "2": 2}.get(os.environ.get("MHPPO_ROLLOUT_GRAPH", "1"), 1)
 
 
+class EvalStats:
+    """The streaming evaluation statistics' device state for one env handle (include/mhppo.h
+    mhppo_eval_stats_*): begin() zeroes it, row(obs, t, T) consumes row t of the current episode
+    of every env (obs float32 [N, obs_dim] on the env's device: the live pre-step observation, or
+    a row of a recorded trajectory), fold() returns the float64 [MHPPO_EVS_N] sums.  Calls go to
+    the env's device's current stream.  ValueError for a layout get_average rejects (4cars)."""
+
+    def __init__(self, venv):
+        from .stats import EVS_N, check_variant
+        check_variant(venv.variant)
+        self.venv = venv
+        n = _lib.eval_stats_bytes(venv.handle)
+        self.state = torch.empty((n + 7) // 8, dtype=torch.float64, device=venv.device)
+        self.n_sums = EVS_N
+
+    def _st(self):
+        return _lib.stream_ptr(device=self.venv.device)
+
+    def begin(self):
+        _lib.eval_stats_begin(self.venv.handle, _lib.ptr(self.state), self._st())
+
+    def row(self, obs, t, T):
+        v = self.venv
+        if (obs.dtype != torch.float32 or obs.device != v.device or tuple(obs.shape) != (v.n_envs, v.obs_dim)
+                or not obs.is_contiguous()):
+            raise ValueError(f"EvalStats.row takes a contiguous float32 [{v.n_envs}, {v.obs_dim}] on {v.device}")
+        _lib.eval_stats_row(v.handle, _lib.ptr(obs), int(t), int(T), _lib.ptr(self.state), self._st())
+
+    def fold(self):
+        sums = torch.empty(self.n_sums, dtype=torch.float64, device=self.venv.device)
+        _lib.eval_stats_fold(self.venv.handle, _lib.ptr(self.state), _lib.ptr(sums), self._st())
+        return sums
+
+
 class RolloutGPU:
     def __init__(self, venv, T=None, valu_policy=False, parts=None):
         if venv.variant == "4cars2":
@@ -176,6 +210,41 @@ class RolloutGPU:
         saved = cat["saved"].reshape(-1).bool()
         return (cat["obs"].reshape(-1, venv.obs_dim), cat["acts"].reshape(-1, S), cat["rews_c"].reshape(-1, S),
                 cat["rews_d"].reshape(-1, S)[saved], cat["waiting"].reshape(-1, P)[saved].reshape(-1))
+
+    def evaluate_stats(self, actor_cross, actor_wait, actor_choice, episodes=1, choix=False):
+        """evaluate() reduced on the device to get_average's sums (opt-in, beyond the reference):
+        the same resets and steps in the same order — the env ends in the state evaluate(episodes)
+        leaves it in — but no history is kept: each step's pre-step observation goes through
+        mhppo_eval_stats_row into per-env accumulators, folded once at the end.  Memory is O(N)
+        whatever `episodes` is; nothing is allocated per episode and nothing read back.
+        Returns float64 [MHPPO_EVS_N] on the env's device (mhppo.stats.stats_from_sums makes the
+        dict; the sums add across ranks).  Episodes are the true ones, N * episodes in all, also
+        under choix=True, where get_average's equal-width runs merge them into one."""
+        L = _lib.lib()
+        venv, N, S, P, T = self.venv, self.N, self.S, self.P, self.T
+        dev = venv.device
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        acc = EvalStats(venv)
+        E = dict(obs=z((N, venv.obs_dim), torch.float32), a_d=z((N, S, P), torch.int32),
+                 trig=z(N, torch.uint8), ep_min=z((N, S), torch.float64), saved=z((T, N), torch.uint8))
+        b = _lib.EvalBufs()  # the histories stay NULL: mhppo_eval_step skips their stores
+        for k, v in E.items():
+            setattr(b, k, ctypes.c_void_p(v.data_ptr()))
+        b.T = T
+        mc, tc = actor_cross.mlp_desc()
+        mw, tw = actor_wait.mlp_desc()
+        md, td = actor_choice.mlp_desc()
+        st = _lib.stream_ptr(device=dev)
+        acc.begin()
+        for _ in range(episodes):
+            _lib.check(L.mhppo_env_reset(venv.handle, _lib.ptr(E["obs"]), st))
+            if choix:
+                _lib.check(L.mhppo_env_choix_test(venv.handle, _lib.ptr(E["obs"]), st))
+            for t in range(T):
+                acc.row(E["obs"], t, T)
+                _lib.check(L.mhppo_eval_step(venv.handle, ctypes.byref(mc), ctypes.byref(mw), ctypes.byref(md), t,
+                                             ctypes.byref(b), st))
+        return acc.fold()
 
     def check(self):
         """Raise MhppoNaNError (a ValueError, as the reference's torch.distributions raise) if

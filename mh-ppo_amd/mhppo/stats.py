@@ -31,6 +31,71 @@ _CAR_W = {"scalable": 7, "coop": 6, "naif": 6, "stop": 6}
 _ENV_W = {"scalable": 4, "coop": 3, "naif": 3, "stop": 3}
 
 
+# include/mhppo.h MHPPO_EVS_*: the streaming statistics' sums, in order
+EVS_NAMES = ("ROWS", "V0", "V0_SQ", "ABSA0", "A0", "A0_SQ", "ABSVP0", "ABSVP0_SQ", "EPISODES", "N_PED", "PEDT",
+             "PEDT_SQ", "WAIT", "WAIT_SQ", "N_CAR", "CART", "CART_SQ", "FC", "IC", "N_YSPEED", "YSPEED", "YSPEED_SQ",
+             "N_YTIME", "YTIME", "YTIME_SQ", "YIELD", "GO", "N_CS", "CS", "SC_YY", "SC_GG", "SC_GY", "SC_YG")
+EVS = {name: i for i, name in enumerate(EVS_NAMES)}
+EVS_N = len(EVS_NAMES)
+EVS_COUNTS = ("ROWS", "EPISODES", "N_PED", "N_CAR", "N_YSPEED", "N_YTIME", "YIELD", "GO", "N_CS", "CS", "SC_YY",
+              "SC_GG", "SC_GY", "SC_YG")
+
+
+def check_variant(variant):
+    """The ValueError get_average raises for a layout it is not defined for (the 4cars drivers')."""
+    if variant not in _CAR_W:
+        raise ValueError(f"get_average is defined for the scalable/coop/naif/stop drivers' observation "
+                         f"layout (car|env|ped), not {variant!r}")
+
+
+def stats_from_sums(sums, nb_car):
+    """get_average's dict from the MHPPO_EVS_N float64 sums of the streaming statistics
+    (mhppo_eval_stats_fold, RolloutGPU.evaluate_stats; include/mhppo.h): a pure function.
+    mean = S / n (NaN at n = 0); the torch entries' std unbiased (NaN at n <= 1), the waiting
+    times' the population one; variances clamped at 0; shares integer / integer.  The
+    scenario_* keys only for nb_car == 2.  Non-finite sums stay what float arithmetic makes of
+    them, as in get_average (an absent car's infinite no-interaction time, inf - inf)."""
+    s = [float(x) for x in (sums.tolist() if hasattr(sums, "tolist") else sums)]
+    if len(s) != EVS_N:
+        raise ValueError(f"stats_from_sums takes {EVS_N} sums (MHPPO_EVS_N), got {len(s)}")
+    nan = float("nan")
+    g = lambda name: s[EVS[name]]
+    cnt = lambda name: int(round(g(name)))
+
+    def mean(name, n):
+        return g(name) / n if n > 0 else nan
+
+    def std(name, n, ddof):
+        if n - ddof <= 0:
+            return nan
+        var = (g(name + "_SQ") - g(name) * g(name) / n) / (n - ddof)
+        return max(var, 0.0) ** 0.5 if var == var else nan
+
+    def share(name, n):  # integer / integer, ZeroDivisionError-free
+        return cnt(name) / n if n > 0 else nan
+
+    rows, n_ep, n_ped, n_car = cnt("ROWS"), cnt("EPISODES"), cnt("N_PED"), cnt("N_CAR")
+    n_ys, n_yt, n_cs = cnt("N_YSPEED"), cnt("N_YTIME"), cnt("N_CS")
+    out = {
+        "mean_speed_car0": mean("V0", rows), "std_speed_car0": std("V0", rows, 1),
+        "mean_abs_acc_car0": mean("ABSA0", rows), "std_acc_car0": std("A0", rows, 1),
+        "mean_abs_speed_ped0": mean("ABSVP0", rows), "std_abs_speed_ped0": std("ABSVP0", rows, 1),
+        "mean_speed_yielding_cars": mean("YSPEED", n_ys), "std_speed_yielding_cars": std("YSPEED", n_ys, 1),
+        "interaction_cost": mean("IC", n_ep), "interaction_cost_max": mean("FC", n_ped + n_car),
+        "mean_pass_time_yielding_cars": mean("YTIME", n_yt), "std_pass_time_yielding_cars": std("YTIME", n_yt, 1),
+        "mean_pass_time_cars": mean("CART", n_car), "std_pass_time_cars": std("CART", n_car, 1),
+        "mean_pass_time_peds": mean("PEDT", n_ped), "std_pass_time_peds": std("PEDT", n_ped, 1),
+        "yield_share": share("YIELD", n_ep), "go_share": share("GO", n_ep),
+        "mean_waiting_time": mean("WAIT", n_ped), "std_waiting_time": std("WAIT", n_ped, 0),
+        "could_stop_share": share("CS", n_cs),
+        "episodes": n_ep,
+    }
+    if nb_car == 2:
+        out.update({"scenario_yield_yield": share("SC_YY", n_ep), "scenario_go_go": share("SC_GG", n_ep),
+                    "scenario_go_yield": share("SC_GY", n_ep), "scenario_yield_go": share("SC_YG", n_ep)})
+    return out
+
+
 def _repeated_add(step, n):
     """w[k] = step + step + ... (k Python float additions, left to right)."""
     w = np.zeros(n + 1)
@@ -43,9 +108,7 @@ def _repeated_add(step, n):
 
 def split_states(states, variant, nb_car, nb_ped, nb_lines):
     """ep_car, ep_env, ep_ped, ep_cross as the reference cell builds them (:1081-1091)."""
-    if variant not in _CAR_W:
-        raise ValueError(f"get_average is defined for the scalable/coop/naif/stop drivers' observation "
-                         f"layout (car|env|ped), not {variant!r}")
+    check_variant(variant)
     S = 2 * nb_lines if variant == "scalable" else nb_car
     cw, ew = _CAR_W[variant], _ENV_W[variant]
     st = torch.as_tensor(states, dtype=torch.float32)
