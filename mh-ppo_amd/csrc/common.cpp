@@ -1,4 +1,5 @@
-// common.cpp — thread-local last-error message, version string and the per-device scratch buffer.
+// common.cpp — thread-local last-error message, version string, the per-device scratch buffer, the
+// cached CU counts and the dynamic-LDS limits.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -38,6 +39,28 @@ double *scratch(size_t n) {
     s.n = n;
   }
   return s.p;
+}
+
+int device_cus(int dev) {
+  static std::atomic<int> cus[MAX_DEVICES];
+  const bool tracked = dev >= 0 && dev < MAX_DEVICES;
+  if (tracked)
+    if (const int n = cus[dev].load(std::memory_order_relaxed)) return n;
+  int n = 256;
+  (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+  if (tracked) cus[dev].store(n, std::memory_order_relaxed);
+  return n;
+}
+
+int allow_dynamic_lds(const void *kernel, size_t bytes, LdsLimit &limit) {
+  if (bytes <= 64 * 1024) return MHPPO_OK;
+  int dev = -1;
+  CHECK_HIP(hipGetDevice(&dev));
+  const bool tracked = dev >= 0 && dev < MAX_DEVICES;
+  if (tracked && limit.bytes[dev].load(std::memory_order_relaxed) >= (int)bytes) return MHPPO_OK;
+  CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (tracked) limit.bytes[dev].store((int)bytes, std::memory_order_relaxed);
+  return MHPPO_OK;
 }
 }  // namespace mhppo
 

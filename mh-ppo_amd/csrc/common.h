@@ -1,9 +1,12 @@
 // common.h — what the libmhppo.so translation units share on the host side: error reporting, the
-// device guard of an ABI call and the per-device scratch buffer.
+// device guard of an ABI call, the per-device scratch buffer, the cached CU count and the
+// dynamic-LDS limit of a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+
+#include <atomic>
 
 namespace mhppo {
 int set_error(int code, const char *fmt, ...);
@@ -35,6 +38,19 @@ constexpr int MAX_DEVICES = 16;
 // use is stream-ordered, and a call's contents mean nothing to the next.  (Hidden: the library's
 // dynamic symbol list stays what it was.)
 __attribute__((visibility("hidden"))) double *scratch(size_t n);
+
+// The multiprocessor (CU) count of device `dev`, asked once per device (256 if the query fails; a
+// device number outside the table is asked every time).
+__attribute__((visibility("hidden"))) int device_cus(int dev);
+
+// Dynamic LDS above the 64 KB a kernel gets by default: allow_dynamic_lds raises `kernel`'s limit
+// on the current device to `bytes`, at most once per device and size (`limit`, one per kernel,
+// static storage: what it was last raised to; a device number outside the table sets the attribute
+// on every call).  MHPPO_OK, or the error already set.
+struct LdsLimit {
+  std::atomic<int> bytes[MAX_DEVICES];
+};
+__attribute__((visibility("hidden"))) int allow_dynamic_lds(const void *kernel, size_t bytes, LdsLimit &limit);
 }  // namespace mhppo
 using mhppo::set_error;
 

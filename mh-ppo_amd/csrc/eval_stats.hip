@@ -7,12 +7,13 @@
 //               would fetch every line anyway, 64 lines per load instruction; instead a block copies
 //               its envs' rows — one contiguous run of floats — into LDS with coalesced loads and
 //               each lane reads its row from there (row stride odd: conflict-free).
-//   k_evs_fold  one block per sum: the per-env accumulators of that sum folded as
-//               ppo_batch.hip's k_sum_partials_wide folds per-block partials (four independent chains
-//               per thread, then a fixed tree), written — not added — to sums.
+//   k_evs_fold  one block per sum: the per-env accumulators of that sum folded in the fixed
+//               order of block_prims.h (k_fold: 1024 threads, four chains per thread, then the
+//               tree), written — not added — to sums.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mhppo.h"
+#include "block_prims.h"
 #include "common.h"
 #include "eval_stats_terms.h"
 
@@ -47,22 +48,7 @@ __global__ void __launch_bounds__(ROW_TPB)
   evs::row<false>(s_rows + threadIdx.x * rs, L, t, T, v);
 }
 
-__global__ void __launch_bounds__(FOLD_TPB) k_evs_fold(const double *acc, int N, double *sums) {
-  __shared__ double sh[FOLD_TPB];
-  const double *p = acc + (size_t)blockIdx.x * N;
-  double a[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < N; b += 4 * FOLD_TPB)
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-      if (b + u * FOLD_TPB < N) a[u] += p[b + u * FOLD_TPB];
-  sh[threadIdx.x] = (a[0] + a[1]) + (a[2] + a[3]);
-  __syncthreads();
-  for (int w = FOLD_TPB / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sums[blockIdx.x] = sh[0];
-}
+constexpr auto k_evs_fold = k_fold<FOLD_TPB, 4, false>;
 
 int env_layout(const mhppo_env *env, evs::Layout &L) {
   const Cfg &c = env_cfg(env);

@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 
 #include "../../include/mhppo.h"
 #include "common.h"
@@ -42,7 +41,6 @@ namespace {
 // parallelism (256 tiles: 64 blocks).  (Smaller blocks for small B, to reach more CUs, were measured no faster: a wave has its
 // SIMD to itself either way, and 64 threads stage the images more slowly.)
 constexpr int GW = 4, MAX_BLOCKS = 512, SPLIT_TILES = MAX_BLOCKS * GW / 2;
-int64_t n_tiles(int64_t B) { return (B + 31) / 32; }
 
 // LDS ordering inside one wave (its own input slots): the DS queue is in order per wave, the
 // fences keep the compiler from moving the accesses
@@ -161,28 +159,14 @@ int check_critic(const mhppo_mlp *m, const char *what) {
   return MHPPO_OK;
 }
 
-// Dynamic LDS above the 64 KB a kernel gets by default (wide critics): the limit is raised once
-// per device and size, not on every launch.
-constexpr int MAX_DEVICES = 64;
-std::atomic<int> g_lds_allowed[MAX_DEVICES];
-int allow_lds(size_t bytes) {
-  if (bytes <= 64 * 1024) return MHPPO_OK;
-  int dev = -1;
-  CHECK_HIP(hipGetDevice(&dev));
-  const bool tracked = dev >= 0 && dev < MAX_DEVICES;
-  if (tracked && g_lds_allowed[dev].load(std::memory_order_relaxed) >= (int)bytes) return MHPPO_OK;
-  CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gae_tm), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bytes));
-  if (tracked) g_lds_allowed[dev].store((int)bytes, std::memory_order_relaxed);
-  return MHPPO_OK;
-}
+LdsLimit g_lds_limit;  // k_gae_tm's dynamic LDS above the default 64 KB (wide critics)
 
 int launch(const float *W0, const float *W1, int n_in, const float *obs_tm, const double *rew_tm, const int64_t *pos,
            const int8_t *bucket, int64_t B, int T, double gamma, double lambda, float *ret_tm, float *value_tm,
            hipStream_t s) {
   const Img g = img_layout(n_in, 1);
   const size_t shm = ((size_t)(W1 ? 2 : 1) * g.size + (size_t)2 * GW * xtile_floats(g)) * sizeof(float);
-  if (int rc = allow_lds(shm)) return rc;
+  if (int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_gae_tm), shm, g_lds_limit)) return rc;
   const int split = W1 && n_tiles(B) <= SPLIT_TILES;
   const int64_t units = split ? 2 * n_tiles(B) : n_tiles(B);
   const int nb = (int)std::min<int64_t>((units + GW - 1) / GW, MAX_BLOCKS);

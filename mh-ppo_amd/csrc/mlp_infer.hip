@@ -5,12 +5,14 @@
 // Both run 32-row tiles on f32 MFMA in the rollout's arithmetic (mlp_infer_tile.h): a wave stages
 // its tile's rows through LDS with coalesced loads, the nets' permuted weight images are staged
 // once per block, and a block walks its tiles in a fixed order (grid-stride), so the sums depend
-// only on M.  The per-row terms are the host+device functions of mlp_infer_terms.h.
+// only on M.  The per-row terms are the host+device functions of mlp_infer_terms.h; the block
+// partials of the diagnostics are folded by block_prims.h's k_fold.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "../../include/mhppo.h"
+#include "block_prims.h"
 #include "common.h"
 #include "mlp_infer_terms.h"
 #include "mlp_infer_tile.h"
@@ -24,7 +26,6 @@ constexpr int ITPB = 256, IWAVES = ITPB / 64;
 // per CU on 256 CUs: k_ppo_diag's register bound) walking the rest grid-stride.  A function of M alone: the order
 // of the diagnostics' sums, and with it their bits, is the same on every device.
 constexpr int MAX_BLOCKS = 512;
-int64_t n_tiles(int64_t M) { return (M + 31) / 32; }
 int n_blocks(int64_t M) { return (int)std::min<int64_t>((n_tiles(M) + IWAVES - 1) / IWAVES, MAX_BLOCKS); }
 
 struct NetArg {
@@ -146,21 +147,8 @@ __global__ void __launch_bounds__(ITPB) __attribute__((amdgpu_waves_per_eu(2)))
   }
 }
 
-// sums[k] = the block partials of term k: a fixed strided subset per thread, then a fixed tree
-// (ppo_loss.hip k_sum_partials' order; writes instead of adding)
-__global__ void __launch_bounds__(ITPB) k_diag_fold(const double *__restrict__ partials, int nblocks, double *sums) {
-  __shared__ double sh[ITPB];
-  const int k = blockIdx.x;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += ITPB) s += partials[(size_t)k * nblocks + b];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int q = ITPB / 2; q > 0; q >>= 1) {
-    if ((int)threadIdx.x < q) sh[threadIdx.x] += sh[threadIdx.x + q];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) sums[k] = sh[0];
-}
+// sums[k] = the fold of term k's block partials (one chain per thread, then the tree), written
+constexpr auto k_diag_fold = k_fold<ITPB, 1, false>;
 
 int check_net(const mhppo_mlp *m, const char *what) {
   if (!m || !m->packed) return set_error(MHPPO_EINVAL, "%s: null pointer", what);
@@ -173,13 +161,12 @@ int check_net(const mhppo_mlp *m, const char *what) {
   return MHPPO_OK;
 }
 
-// dynamic LDS above the 64 KB a kernel gets by default (the wide choice heads' diagnostics)
-template <typename K>
-int allow_lds(K kernel, size_t bytes) {
-  if (bytes > 64 * 1024)
-    CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)bytes));
-  return MHPPO_OK;
+// dynamic LDS above the 64 KB a kernel gets by default (the wide choice heads' diagnostics); the
+// kernel is the template argument, so each instantiation has a limit table of its own
+template <auto KERNEL>
+int allow_lds(size_t bytes) {
+  static LdsLimit limit;
+  return allow_dynamic_lds(reinterpret_cast<const void *>(KERNEL), bytes, limit);
 }
 }  // namespace
 
@@ -196,10 +183,10 @@ int mhppo_mlp_forward(const mhppo_mlp *net, const float *X, int64_t M, float *ou
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)n_blocks(M));
   if (net->n_out == 2) {
-    if (int rc = allow_lds(k_mlp_forward<2>, shm)) return rc;
+    if (int rc = allow_lds<k_mlp_forward<2>>(shm)) return rc;
     hipLaunchKernelGGL(k_mlp_forward<2>, grid, dim3(ITPB), shm, s, a, (int)net->kind, (int)net->n_in, X, M, out);
   } else {
-    if (int rc = allow_lds(k_mlp_forward<1>, shm)) return rc;
+    if (int rc = allow_lds<k_mlp_forward<1>>(shm)) return rc;
     hipLaunchKernelGGL(k_mlp_forward<1>, grid, dim3(ITPB), shm, s, a, (int)net->kind, (int)net->n_in, X, M, out);
   }
   CHECK_HIP(hipGetLastError());
@@ -235,11 +222,11 @@ int mhppo_ppo_diag(const mhppo_mlp *actor, const mhppo_mlp *critic, const float 
   const int nb = n_blocks(M);
   double *part = static_cast<double *>(work);
   if (actor->kind == 2) {
-    if (int rc = allow_lds(k_ppo_diag<2>, shm)) return rc;
+    if (int rc = allow_lds<k_ppo_diag<2>>(shm)) return rc;
     hipLaunchKernelGGL(k_ppo_diag<2>, dim3(nb), dim3(ITPB), shm, s, a, c, (int)actor->n_in, X, M, act, logp_old, ret,
                        part);
   } else {
-    if (int rc = allow_lds(k_ppo_diag<1>, shm)) return rc;
+    if (int rc = allow_lds<k_ppo_diag<1>>(shm)) return rc;
     hipLaunchKernelGGL(k_ppo_diag<1>, dim3(nb), dim3(ITPB), shm, s, a, c, (int)actor->n_in, X, M, act, logp_old, ret,
                        part);
   }

@@ -37,6 +37,8 @@ __host__ __device__ inline Img img_layout(int n_in, int n_out) {
   return g;
 }
 __host__ __device__ inline int xtile_floats(const Img &g) { return (32 * g.S1 + 3) / 4 * 4; }
+// 32-row tiles of M rows
+inline int64_t n_tiles(int64_t M) { return (M + 31) / 32; }
 
 // One torch-packed net (W1 b1 W2 b2 W3 b3 W4 b4) into its LDS image: the rows of W1 / W2 / W3 and
 // the entries of b1 / b2 / b3 at the permuted row of their neuron, W1's padding columns zeroed.

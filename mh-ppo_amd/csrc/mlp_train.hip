@@ -31,7 +31,6 @@ struct Work {
   double *d = nullptr;
   double *t = nullptr;
   int nw = 0;
-  int cus = 0;
   // The split kernels write ONE float64 partial per block (np <= NW_MAX doubles each), not a float
   // one per wave: a launch of `blocks` blocks per net has blocks * WAVES slots per net, i.e.
   // blocks * WAVES * NW_MAX floats, which hold blocks * NW_MAX doubles as long as WAVES floats are
@@ -70,13 +69,7 @@ Work *device_work(int dev, hipStream_t s) {
     g_work_stream[dev][k] = s;
     g_work_used[dev] = k + 1;
   }
-  Work &wk = g_work[dev][k];
-  if (wk.cus == 0) {
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    wk.cus = cus;
-  }
-  return &wk;
+  return &g_work[dev][k];
 }
 
 // What a launch needs besides its arguments: the stream's partial buffers and the grid (one block
@@ -105,7 +98,7 @@ int prepare_launch(hipStream_t s, int64_t M, const float *X, XAlign xa, int wave
   if (xa == X_16B_AFTER_LOOKUP && misaligned)
     return set_error(MHPPO_EINVAL, "X must be 16-byte aligned (LDS-DMA rows)");
   const int64_t tiles = (M + 31) / 32;
-  L.blocks = (int)std::max<int64_t>(1, std::min<int64_t>(L.wk->cus, (tiles + waves - 1) / waves));
+  L.blocks = (int)std::max<int64_t>(1, std::min<int64_t>(mhppo::device_cus(dev), (tiles + waves - 1) / waves));
   L.nw = L.blocks * waves;
   if (!ensure_work(*L.wk, nets * L.nw)) return set_error(MHPPO_ENOMEM, "mlp_train partials");
   return MHPPO_OK;

@@ -1,16 +1,18 @@
 // ppo_batch.hip — from a finished rollout's time-major records to the update's batches (+ C-ABI):
 //   k_returns / k_returns_tm   the reward-to-go scan (mhppo_returns_scan / _scan_tm)
 //   k_bucket_scatter           both segment-major buckets in one pass over the records, optionally
-//                              with their reward sums, folded by k_sum_partials_wide
+//                              with their reward sums, folded by k_fold<1024, 4, add>
 //                              (mhppo_bucket_scatter / _scatter_sums)
 //   k_plan_count / _scan / _place   the bucket positions, the choice batch and the host's one info
 //                              record (mhppo_bucket_plan; scratch size: mhppo_bucket_work_bytes)
-// Every sum has a fixed order: the same call gives the same bits.
+// Every sum has a fixed order (block_prims.h: the fold and the ballot rank): the same call gives
+// the same bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "../../include/mhppo.h"
+#include "block_prims.h"
 #include "common.h"
 #include "launch1d.h"
 #include "ppo_math.h"  // NF_C
@@ -65,7 +67,7 @@ constexpr int BTPB = MHPPO_BK_TPB;
 }
 // SUMS (mhppo_bucket_scatter_sums): partials[b * nblocks + block] = the block's sum of
 // (double)(float)rew over its records of bucket b (wave butterflies, then the waves in order: a
-// fixed order), folded by k_sum_partials_wide.
+// fixed order), folded by k_fold_wide.
 template <bool SUMS>
 __global__ void __launch_bounds__(bk::BTPB)
     k_bucket_scatter(const int64_t *__restrict__ pos, const int8_t *__restrict__ bucket, int64_t NS, int T,
@@ -159,10 +161,10 @@ __global__ void __launch_bounds__(bk::BTPB)
 }
 
 // ------------------------------------------------------------ bucket plan
-// mhppo_bucket_plan: what bucket_segments needs before its one host read, in three launches — the
-// pattern of the head lists and the record ranks (rollout_lists.h; no block waits on another):
-// per-block counts (k_plan_count), ONE block scans them and writes the mhppo_bucket_info record
-// (k_plan_scan), then every block places its segments by wave prefix (k_plan_place).
+// mhppo_bucket_plan: what bucket_segments needs before its one host read, in three launches (no
+// block waits on another): per-block counts (k_plan_count), ONE block scans them and writes the
+// mhppo_bucket_info record (k_plan_scan), then every block places its segments by their rank in
+// the block (k_plan_place; block_prims.h block_rank).
 struct PlanSeg {
   int64_t base;  // the segment's choice row: s P + closest[s]
   int a_car;     // a_d there (the choice batch's action)
@@ -191,36 +193,25 @@ __global__ void __launch_bounds__(TPB)
                  const uint8_t *__restrict__ exist, const double *__restrict__ ep_min, int fix, int nblk,
                  int32_t *__restrict__ cnt, double *__restrict__ epart, int64_t *__restrict__ pos,
                  int8_t *__restrict__ bucket) {
-  __shared__ int wsum[PLAN_NC][TPB / 64];
-  __shared__ double sh[TPB];
   const int64_t s = (int64_t)blockIdx.x * TPB + threadIdx.x;
   bool f[PLAN_NC] = {false, false, false, false, false};
-  double e = 0.0;
+  double e[1] = {0.0};
   if (s < NS) {
     const PlanSeg q = plan_seg(s, S, P, a_d, closest, exist, fix);
     f[0] = q.cross, f[1] = q.wait, f[2] = q.exist;
     f[3] = q.exist && q.a_car == 0, f[4] = q.exist && q.a_car == 1;
-    if (q.exist) e = (double)(float)ep_min[s];  // the choice batch's reward (float32), summed in float64
+    if (q.exist) e[0] = (double)(float)ep_min[s];  // the choice batch's reward (float32), summed in float64
     pos[s] = -1;  // k_plan_place fills in the bucketed segments (records, in the compact layout)
     bucket[s] = 0;
   }
+  int before[PLAN_NC], c[PLAN_NC];
+  block_rank<TPB>(f, before, c);
+  block_sum<TPB>(e);
+  if (threadIdx.x == 0) {
 #pragma unroll
-  for (int k = 0; k < PLAN_NC; k++) {
-    const uint64_t m = __ballot(f[k]);
-    if ((threadIdx.x & 63) == 0) wsum[k][threadIdx.x >> 6] = __popcll(m);
+    for (int k = 0; k < PLAN_NC; k++) cnt[(size_t)k * nblk + blockIdx.x] = c[k];
+    epart[blockIdx.x] = e[0];
   }
-  sh[threadIdx.x] = e;
-  __syncthreads();
-  for (int st = TPB / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x < PLAN_NC) {
-    int c = 0;
-    for (int w = 0; w < TPB / 64; w++) c += wsum[threadIdx.x][w];
-    cnt[(size_t)threadIdx.x * nblk + blockIdx.x] = c;
-  }
-  if (threadIdx.x == 0) epart[blockIdx.x] = sh[0];
 }
 
 // one block: base[k][b] = the sum of cnt[k][0 .. b) for k = cross, wait, existing (tiles of TPB
@@ -229,7 +220,6 @@ __global__ void __launch_bounds__(TPB)
     k_plan_scan(const int32_t *__restrict__ cnt, const double *__restrict__ epart, int nblk,
                 const int32_t *__restrict__ status, int32_t *__restrict__ base, mhppo_bucket_info *__restrict__ info) {
   __shared__ int wsum[TPB / 64];
-  __shared__ double sh[TPB];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   int64_t total[PLAN_NC];
 #pragma unroll
@@ -256,14 +246,8 @@ __global__ void __launch_bounds__(TPB)
     }
     total[k] = carry;
   }
-  double e = 0.0;  // k_sum_partials' order: a fixed strided subset per thread, then a fixed tree
-  for (int b = tid; b < nblk; b += TPB) e += epart[b];
-  sh[tid] = e;
-  __syncthreads();
-  for (int st = TPB / 2; st > 0; st >>= 1) {
-    if (tid < st) sh[tid] += sh[tid + st];
-    __syncthreads();
-  }
+  double e[1] = {strided_sum<TPB, 1>(epart, nblk)};  // the fold's order: one chain, TPB threads
+  block_sum<TPB>(e);
   if (tid == 0) {
     info->n_cross = total[0];
     info->n_wait = total[1];
@@ -273,7 +257,7 @@ __global__ void __launch_bounds__(TPB)
     info->counts[1] = (double)total[4];
     info->rew_sums[0] = 0.0;  // the scatter's fold adds the cross / wait sums
     info->rew_sums[1] = 0.0;
-    info->rew_sums[2] = sh[0];
+    info->rew_sums[2] = e[0];
   }
 }
 
@@ -285,29 +269,18 @@ __global__ void __launch_bounds__(TPB)
                  const int32_t *__restrict__ base, const mhppo_bucket_info *__restrict__ info,
                  int64_t *__restrict__ pos, int8_t *__restrict__ bucket, float *__restrict__ c_obs,
                  int32_t *__restrict__ c_act, float *__restrict__ c_logp, float *__restrict__ c_ret) {
-  __shared__ int wsum[3][TPB / 64];
   __shared__ int64_t s_src[TPB];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t s = (int64_t)blockIdx.x * TPB + tid;
   PlanSeg q;
   q.base = 0, q.a_car = 0, q.exist = q.cross = q.wait = false;
   if (s < NS) q = plan_seg(s, S, P, a_d, closest, exist, fix);
-  const uint64_t mc = __ballot(q.cross), mw = __ballot(q.wait), me = __ballot(q.exist);
-  if (lane == 0) {
-    wsum[0][w] = __popcll(mc);
-    wsum[1][w] = __popcll(mw);
-    wsum[2][w] = __popcll(me);
-  }
-  __syncthreads();
-  int wc = 0, ww = 0, we = 0, ne = 0;
-  for (int k = 0; k < TPB / 64; k++) {
-    if (k < w) wc += wsum[0][k], ww += wsum[1][k], we += wsum[2][k];
-    ne += wsum[2][k];
-  }
-  const uint64_t lt = lane ? ((1ull << lane) - 1) : 0ull;
-  const int64_t ci = (int64_t)base[blockIdx.x] + wc + __popcll(mc & lt);                      // cross segments before s
-  const int64_t wi = (int64_t)base[(size_t)nblk + blockIdx.x] + ww + __popcll(mw & lt);       // wait segments before s
-  const int er = we + __popcll(me & lt);  // existing segments before s in this block
+  const bool f[3] = {q.cross, q.wait, q.exist};
+  int before[3], total[3];
+  block_rank<TPB>(f, before, total);
+  const int64_t ci = (int64_t)base[blockIdx.x] + before[0];                 // cross segments before s
+  const int64_t wi = (int64_t)base[(size_t)nblk + blockIdx.x] + before[1];  // wait segments before s
+  const int er = before[2], ne = total[2];  // existing segments before s in this block, and in all of it
   const int64_t eb = base[2 * (size_t)nblk + blockIdx.x];
   // the wait bucket starts at the cross count rounded up to a multiple of 4 (bucket_segments)
   const int64_t w0 = (info->n_cross + 3) / 4 * 4;
@@ -335,26 +308,9 @@ __global__ void __launch_bounds__(TPB)
   }
 }
 
-// ppo_loss.hip's k_sum_partials for many partials (the bucket scatter's: two per block, 20 480 blocks at 65 536
-// envs x 4 slots): 1024 threads with four independent chains each, so a thread's loads are 4 deep
-// rather than one serial chain of nblocks / 256 (34 us there); the order is as fixed
+// the fold of the scatter's partials (two per block: many), added to rew_sums
 constexpr int FOLD_TPB = 1024;
-__global__ void __launch_bounds__(FOLD_TPB) k_sum_partials_wide(const double *partials, int nblocks, double *out) {
-  __shared__ double sh[FOLD_TPB];
-  const double *p = partials + (size_t)blockIdx.x * nblocks;
-  double a[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < nblocks; b += 4 * FOLD_TPB)
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-      if (b + u * FOLD_TPB < nblocks) a[u] += p[b + u * FOLD_TPB];
-  sh[threadIdx.x] = (a[0] + a[1]) + (a[2] + a[3]);
-  __syncthreads();
-  for (int w = FOLD_TPB / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] += sh[0];
-}
+constexpr auto k_fold_wide = k_fold<FOLD_TPB, 4, true>;
 
 }  // namespace
 
@@ -418,7 +374,7 @@ int mhppo_bucket_scatter_sums(const int64_t *pos, const int8_t *bucket, int64_t 
   double *part = (double *)work;
   hipLaunchKernelGGL(k_bucket_scatter<true>, g, dim3(bk::BTPB), 0, s, pos, bucket, NS, (int)T, obs_tm, act_tm, logp_tm,
                      ret_tm, rew_tm, dst[0], dst[1], part);
-  hipLaunchKernelGGL(k_sum_partials_wide, dim3(2), dim3(FOLD_TPB), 0, s, part, (int)nblocks, rew_sums);
+  hipLaunchKernelGGL(k_fold_wide, dim3(2), dim3(FOLD_TPB), 0, s, part, (int)nblocks, rew_sums);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }

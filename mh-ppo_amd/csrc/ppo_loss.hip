@@ -2,13 +2,14 @@
 // normalisation (mhppo_adv_stats / _adv_normalize), the clipped PPO surrogates of the continuous
 // and the choice actors (mhppo_ppo_cont_fwd_bwd / _ppo_choice_fwd_bwd) and the critic's MSE
 // (mhppo_mse_fwd_bwd), each with its gradient.  Elementwise kernels plus deterministic two-pass
-// reductions in float64 (a fixed summation order: the same call gives the same bits); the block
-// partials live in the per-device scratch (common.h), in stream order.
+// reductions in float64 (a fixed summation order, block_prims.h: the same call gives the same
+// bits); the block partials live in the per-device scratch (common.h), in stream order.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 
 #include "../../include/mhppo.h"
+#include "block_prims.h"
 #include "common.h"
 #include "launch1d.h"
 #include "ppo_math.h"  // surr_and_grad, the MVN constants
@@ -18,40 +19,16 @@ using namespace mhppo;
 namespace {
 
 // ------------------------------------------------- deterministic reductions
-// Pass 1 writes one partial per block (fixed in-block tree order); pass 2 sums the
-// partials in index order into out[k] (+=).  NP = partial arrays per call.
+// Pass 1 writes one partial per block (block_prims.h block_sum: the fixed tree); pass 2 folds the
+// partials into out[k] (+=) with k_fold_add.  NP = partial arrays per call.
 template <int NP>
 __device__ inline void block_reduce_store(double (&v)[NP], double *partials, int nblocks) {
-  __shared__ double sh[NP][TPB];
-#pragma unroll
-  for (int k = 0; k < NP; k++) sh[k][threadIdx.x] = v[k];
-  __syncthreads();
-  for (int s = TPB / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-#pragma unroll
-      for (int k = 0; k < NP; k++) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum<TPB>(v);
   if (threadIdx.x == 0)
 #pragma unroll
-    for (int k = 0; k < NP; k++) partials[(size_t)k * nblocks + blockIdx.x] = sh[k][0];
+    for (int k = 0; k < NP; k++) partials[(size_t)k * nblocks + blockIdx.x] = v[k];
 }
-
-// one block per partial array: each thread sums a fixed strided subset, then a fixed
-// tree — the summation order depends only on nblocks, never on scheduling
-__global__ void __launch_bounds__(TPB) k_sum_partials(const double *partials, int nblocks, int np, double *out) {
-  __shared__ double sh[TPB];
-  int k = blockIdx.x;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += TPB) s += partials[(size_t)k * nblocks + b];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = TPB / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[k] += sh[0];
-}
+constexpr auto k_fold_add = k_fold<TPB, 1, true>;
 
 __global__ void __launch_bounds__(TPB) k_adv_stats(const float *ret, const float *val, int64_t M, double *partials) {
   int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -155,7 +132,7 @@ int mhppo_adv_stats(const float *ret, const float *value, int64_t M, double *sta
   if (!part) return set_error(MHPPO_ENOMEM, "scratch allocation failed");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_adv_stats, g, dim3(TPB), 0, s, ret, value, M, part);
-  hipLaunchKernelGGL(k_sum_partials, dim3(2), dim3(TPB), 0, s, part, (int)g.x, 2, stats);
+  hipLaunchKernelGGL(k_fold_add, dim3(2), dim3(TPB), 0, s, part, (int)g.x, stats);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }
@@ -179,7 +156,7 @@ int mhppo_ppo_cont_fwd_bwd(const float *mu, const float *act, const float *logp_
   if (!part) return set_error(MHPPO_ENOMEM, "scratch allocation failed");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_ppo_cont, g, dim3(TPB), 0, s, mu, act, logp_old, adv, M, inv_m, dmu, part);
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(TPB), 0, s, part, (int)g.x, 1, loss);
+  hipLaunchKernelGGL(k_fold_add, dim3(1), dim3(TPB), 0, s, part, (int)g.x, loss);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }
@@ -194,7 +171,7 @@ int mhppo_ppo_choice_fwd_bwd(const float *probs, const float *logp_old, const fl
   if (!part) return set_error(MHPPO_ENOMEM, "scratch allocation failed");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_ppo_choice, g, dim3(TPB), 0, s, probs, logp_old, adv, M, counts, inv_m2, dprobs, part);
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(TPB), 0, s, part, (int)g.x, 1, loss);
+  hipLaunchKernelGGL(k_fold_add, dim3(1), dim3(TPB), 0, s, part, (int)g.x, loss);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }
@@ -208,7 +185,7 @@ int mhppo_mse_fwd_bwd(const float *value, const float *ret, int64_t M, double in
   if (!part) return set_error(MHPPO_ENOMEM, "scratch allocation failed");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_mse, g, dim3(TPB), 0, s, value, ret, M, inv_m, dv, part);
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(TPB), 0, s, part, (int)g.x, 1, loss);
+  hipLaunchKernelGGL(k_fold_add, dim3(1), dim3(TPB), 0, s, part, (int)g.x, loss);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }

@@ -278,21 +278,15 @@ static int rollout_policy(mhppo_env *env, const mhppo_mlp *actor_cross, const mh
   if (!bufs->rows) return set_error(MHPPO_EINVAL, "the policy step needs the head lists (bufs->rows)");
   if (!(bufs->flags & MHPPO_ROLLOUT_VALU_POLICY)) {
     // persistent 32-row MFMA tiles (grid below)
-    static int cus[mhppo::MAX_DEVICES] = {0};
     const int dev = env_device(env);
     if (dev < 0 || dev >= mhppo::MAX_DEVICES) return set_error(MHPPO_EINVAL, "device %d >= %d", dev, mhppo::MAX_DEVICES);
-    if (!cus[dev]) {
-      int n = 256;
-      (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-      cus[dev] = n;
-    }
     constexpr size_t WPB = PTPB / 64;  // waves per block
     const size_t tiles = R / (32 * (size_t)nparts) + 2;
     // at least the blocks that fit at once (this part's share of them), at most one tile per wave, and
     // beyond the resident blocks ~2 tiles per wave: the waiting blocks start as the first ones drain
     // (cfg4's 8 192 tiles per part: 1 024 blocks, collect -9 %; cfg3: 513, -2 %; cfg2: 65 at one tile
     // per wave, -7 %; profiles/r06_rollout/ab_policy_grid.txt)
-    const size_t resident = (size_t)MHPPO_POLICY_BLOCKS_PER_CU * cus[dev] / nparts + 1;
+    const size_t resident = (size_t)MHPPO_POLICY_BLOCKS_PER_CU * device_cus(dev) / nparts + 1;
     const size_t blocks = std::min<size_t>(std::max<size_t>(resident, (tiles + 2 * WPB - 1) / (2 * WPB)),
                                            (tiles + WPB - 1) / WPB);
     VLAUNCHB(k_policy_mfma, c.variant, dim3((unsigned)blocks), dim3(PTPB), 2 * pol::HEAD * sizeof(float),
