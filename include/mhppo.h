@@ -534,6 +534,66 @@ int mhppo_eval_stats_row(mhppo_env *env, const float *obs, int t, int T, void *s
  * the same call gives the same bits on any stream).  The state is left as it is: more rows may follow. */
 int mhppo_eval_stats_fold(mhppo_env *env, const void *state, double *sums, void *stream);
 
+/* ---- gradient-norm clipping and the Adam step (csrc/adam_clip.hip; opt-in, beyond the reference,
+ * which steps torch.optim.Adam on unclipped gradients, Coop-MH-PPO-scalable.py:806-815) ---- */
+
+/* One launch measures the gradient norm of each of n_nets independent nets, clips it to max_norm
+ * and applies one Adam step to the net, on the torch optimisers' own state tensors: it replaces
+ * torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) + optimizer.step() per net.
+ * A net is an ordered list of up to MHPPO_ADAM_MAX_SEGS segments (Model_PPO: the eight tensors
+ * W1 b1 .. W4 b4 in flat order); a segment's param / grad / exp_avg / exp_avg_sq are separate float32
+ * allocations of n elements, `step` is torch's float32 scalar.  The net's flat element index i runs
+ * 0 .. n_total - 1 across the segments in order (n_total <= 2^30).
+ * The table is HOST memory (the one exception to the convention above): it travels in the kernel
+ * arguments (8 nets x 8 segments x 48 bytes, under the 4 KB a launch takes), so there is no device
+ * table to upload, keep alive or invalidate when an optimiser's state is replaced.
+ *
+ * Arithmetic contract, per net, independent of the other nets of the call (mhppo.ppo.adam_clip_torch
+ * restates it in torch and is compared with the kernel bit for bit):
+ *   ss    = the fold of (double)g_i * (double)g_i (exact) over i = 0 .. n_total - 1 in the order of
+ *           k_fold<1024, 4> (csrc/block_prims.h): thread b's chain u adds elements b + 1024 u,
+ *           b + 1024 u + 4096, ... from +0.0; (a0 + a1) + (a2 + a3); the 1024-thread halving tree
+ *   norm  = sqrt(ss) in float64;  norms[k] = norm  (the norm BEFORE clipping)
+ *   coef  = max_norm / (norm + 1e-6);  s = coef < 1.0 ? (float)coef : 1.0f
+ *           (max_norm = +inf clips nothing and only reports the norms; a NaN coef leaves s = 1)
+ *   per element, float32, no contraction, division and square root correctly rounded:
+ *     g' = g * s
+ *     m  = m + (g' - m) * c1                 c1 = (float)(1 - beta1)
+ *     v  = v * b2 + (g' * g') * c2           b2 = (float)beta2, c2 = (float)(1 - beta2)
+ *     den = sqrtf(v) / q + e                 q  = (float)bias2, e = (float)eps
+ *     p  = p - a * (m / den)                 a  = (float)alpha
+ *   every segment's step = (float)t.  grad is read and never written.
+ * alpha = lr / (1 - beta1^t) and bias2 = sqrt(1 - beta2^t) come from the caller, in float64, for
+ * the step count t AFTER the increment (a device pow would not be reproducible on the host).
+ * This is torch.optim.Adam with weight_decay 0, no amsgrad, no maximize, up to the rounding of
+ * the two bias corrections (torch._fused_adam_ forms them on the device).  There is no skip logic:
+ * a non-finite gradient makes norm inf or NaN, hence s = 0 or 1, and poisons its own net's
+ * moments and parameters through g' as the arithmetic above says (a NaN's sign and payload are
+ * the hardware's); other nets are unaffected.
+ * One block of 1024 threads per net folds, then steps the same net: no block waits on another, no
+ * atomics, nothing depends on the grid: the same call gives the same bits on any stream, whichever
+ * other nets share it.  n_nets == 0 launches nothing.
+ * MHPPO_EINVAL: nets or norms NULL, n_nets outside 0 .. MHPPO_ADAM_MAX_NETS, n_seg outside
+ * 0 .. MHPPO_ADAM_MAX_SEGS, a segment with n < 0 or (n > 0) a NULL pointer, n_total > 2^30,
+ * max_norm NaN or <= 0, a beta outside [0, 1) or NaN. */
+#define MHPPO_ADAM_MAX_NETS 8  /* the product steps at most 6 (three heads' actors and critics) */
+#define MHPPO_ADAM_MAX_SEGS 8
+typedef struct mhppo_adam_seg {
+    float *param;
+    const float *grad;
+    float *exp_avg, *exp_avg_sq;
+    float *step;
+    int64_t n;
+} mhppo_adam_seg;
+typedef struct mhppo_adam_net {
+    mhppo_adam_seg seg[MHPPO_ADAM_MAX_SEGS];
+    int32_t n_seg, reserved;
+    int64_t t;                 /* the step count after this step's increment */
+    double alpha, bias2;       /* lr / (1 - beta1^t), sqrt(1 - beta2^t) */
+    double beta1, beta2, eps;
+} mhppo_adam_net;
+int mhppo_adam_clip(const mhppo_adam_net *nets, int32_t n_nets, double max_norm, double *norms, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

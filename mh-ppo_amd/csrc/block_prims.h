@@ -1,7 +1,8 @@
 // block_prims.h — the block-level primitives of the small kernels (device): the one copy of the
 // fixed-order float64 fold and of the ballot rank that the loss sums (ppo_loss.hip), the bucket
 // plan and the scatter's reward sums (ppo_batch.hip), the diagnostics (mlp_infer.hip), the
-// evaluation statistics (eval_stats.hip) and the head lists / record ranks (rollout_lists.h) use.
+// evaluation statistics (eval_stats.hip), the clip-and-Adam step's gradient norm (adam_clip.hip) and
+// the head lists / record ranks (rollout_lists.h) use.
 // Every sum these kernels make is "the same bits twice and on any stream"; the order that gives
 // those bits is written down here and nowhere else (tests/fold_ref.py restates it in numpy,
 // tests/test_fold_order_gpu.py pins it to the bit).
@@ -58,6 +59,22 @@ __device__ __forceinline__ double strided_sum(const double *__restrict__ p, int 
 #pragma unroll
     for (int u = 0; u < CHAINS; u++)
       if (b + u * NT < n) a[u] += p[b + u * NT];
+  if constexpr (CHAINS == 4) return (a[0] + a[1]) + (a[2] + a[3]);
+  else return a[0];
+}
+
+// The same part of the sum of f(0) .. f(n - 1): the mapped-element form (f: int -> double, called
+// once per element, in the chain's order), for terms that are computed rather than stored.
+template <int NT, int CHAINS, typename F>
+__device__ __forceinline__ double strided_sum(F f, int n) {
+  static_assert(CHAINS == 1 || CHAINS == 4, "strided_sum: one chain or four");
+  double a[CHAINS];
+#pragma unroll
+  for (int u = 0; u < CHAINS; u++) a[u] = 0.0;
+  for (int b = threadIdx.x; b < n; b += CHAINS * NT)
+#pragma unroll
+    for (int u = 0; u < CHAINS; u++)
+      if (b + u * NT < n) a[u] += f(b + u * NT);
   if constexpr (CHAINS == 4) return (a[0] + a[1]) + (a[2] + a[3]);
   else return a[0];
 }

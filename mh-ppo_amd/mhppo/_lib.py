@@ -48,6 +48,18 @@ class EvalBufs(ctypes.Structure):
                 ("rews_d", P), ("waiting", P), ("saved", P), ("T", I32), ("reserved", I32)]
 
 
+class AdamSeg(ctypes.Structure):  # mhppo_adam_seg
+    _fields_ = [("param", P), ("grad", P), ("exp_avg", P), ("exp_avg_sq", P), ("step", P), ("n", I64)]
+
+
+ADAM_MAX_NETS, ADAM_MAX_SEGS = 8, 8
+
+
+class AdamNet(ctypes.Structure):  # mhppo_adam_net
+    _fields_ = [("seg", AdamSeg * ADAM_MAX_SEGS), ("n_seg", I32), ("reserved", I32), ("t", I64), ("alpha", F64),
+                ("bias2", F64), ("beta1", F64), ("beta2", F64), ("eps", F64)]
+
+
 # name: (restype, argtypes)
 _SIGS = {
     "mhppo_env_create": (I32, [ctypes.POINTER(EnvCfg), I32, ctypes.POINTER(P)]),
@@ -105,6 +117,7 @@ _SIGS = {
     "mhppo_eval_stats_begin": (I32, [P, P, P]),
     "mhppo_eval_stats_row": (I32, [P, P, I32, I32, P, P]),
     "mhppo_eval_stats_fold": (I32, [P, P, P, P]),
+    "mhppo_adam_clip": (I32, [P, I32, F64, P, P]),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }
@@ -177,6 +190,13 @@ def eval_stats_row(env, obs, t, T, state, stream):
 
 def eval_stats_fold(env, state, sums, stream):
     return check(lib().mhppo_eval_stats_fold(env, state, sums, stream))
+
+
+def adam_clip(nets, n_nets, max_norm, norms, stream):
+    """mhppo_adam_clip, checked: the one place the entry point is called from (mhppo.ppo.adam_steps
+    with max_grad_norm set), so a run with the knob off can be shown never to reach it.  `nets`: a
+    ctypes array of AdamNet (host), `norms` / `stream`: addresses."""
+    return check(lib().mhppo_adam_clip(ctypes.addressof(nets), n_nets, max_norm, norms, stream))
 
 
 def ptr(t):

@@ -189,6 +189,14 @@ class Algo_PPO:
         self._pending_diag = []   # (pinned [H, DIAG_N] sums, event, iteration, [(name, m, kind)])
         self._diag_heads = None   # update()'s (name, Head) list of the current iteration
         self._diag_work = {}      # per head name: the launch's scratch, allocated once
+        # Opt-in gradient norms (Algo_PPO(max_grad_norm=c)): one entry per iteration,
+        # {"iteration": i, "actor_cross": [10 norms], "critic_cross": [...], ...}: per net trained
+        # that iteration the float64 norm of its (all-reduced) gradient BEFORE clipping at each of
+        # its 10 Adam steps.  They land like the reward curves (asynchronous copy, appended one
+        # iteration later, flushed by curves()).  Not checkpointed: a resumed run starts empty.
+        self.grad_norms = []
+        self._pending_norms = []  # (pinned [10, 2H] norms, event, iteration, head names)
+        self._norms_dev = None    # update()'s (norms tensor, head names) of the current iteration
 
     def nets(self):
         return [self.actor_net_cross, self.actor_net_wait, self.actor_net_choice, self.critic_net_cross,
@@ -228,8 +236,19 @@ class Algo_PPO:
         # Nothing of it is checkpointed; the diagnostics' explained variance and value MSE are then
         # relative to the lambda-returns (they read the buckets' `ret`).
         self.gae_lambda = None
+        # gradient-norm clipping (beyond the reference, whose steps are unbounded): None = off, the
+        # iteration runs exactly the code it always did; a float > 0 clips every net's gradient to
+        # that norm before each of its Adam steps, the first included, on the native clip-and-Adam
+        # launch (mhppo.ppo.adam_clip_steps); inf clips nothing and only records the norms
+        # (self.grad_norms).  A constructor argument, as gae_lambda is: nothing of it is checkpointed.
+        self.max_grad_norm = None
         for k, v in hyperparameters.items():
             setattr(self, k, v)
+        if self.max_grad_norm is not None:
+            c = float(self.max_grad_norm)
+            if not c > 0.0:  # (NaN fails the comparison)
+                raise ValueError(f"max_grad_norm must be None or a float > 0 (inf allowed), not {self.max_grad_norm!r}")
+            self.max_grad_norm = c
         if self.gae_lambda is not None:
             lam = float(self.gae_lambda)
             if not 0.0 <= lam <= 1.0:  # (NaN fails both comparisons)
@@ -274,7 +293,12 @@ class Algo_PPO:
                                       self.optimizer_critic_choice, d["obs"], d["act"], d["logp"], d["ret"], m_d,
                                       counts, per_row=self.fix_choice_loss, exact=self.exact_f32))
                 names.append("choice")
-            losses = ppo.train_epochs(heads, 10, self.grad_bucket) if heads else None
+            clip = getattr(self, "max_grad_norm", None)
+            if clip is None:
+                losses = ppo.train_epochs(heads, 10, self.grad_bucket) if heads else None
+            else:
+                losses, norms = ppo.train_epochs(heads, 10, self.grad_bucket, clip) if heads else (None, None)
+                self._norms_dev = None if norms is None else (norms, names)
             if getattr(self, "_diag_on", False):
                 self._diag_heads = list(zip(names, heads))
         if self.verbose and losses is not None:
@@ -335,6 +359,8 @@ class Algo_PPO:
             diag = getattr(self, "_diag_on", False)
             if diag and self.total_loop % max(1, int(self.diagnostics_every)) == 0:
                 self._queue_diagnostics()
+            if getattr(self, "_norms_dev", None) is not None:
+                self._queue_grad_norms()
             # the reward curves' sums over (cross, wait, choice): from the bucketing pass on the GPU
             # (bucket_segments: fixed-order float64 partials), else torch reductions
             sums = (self.rollout.choice or {}).get("rew_sums")
@@ -369,7 +395,10 @@ class Algo_PPO:
                 self._flush_curves(keep_last=True)
             if diag and len(self._pending_diag) > 1:
                 self._flush_diagnostics(keep_last=True)
+            if len(getattr(self, "_pending_norms", ())) > 1:
+                self._flush_grad_norms(keep_last=True)
         self._flush_curves()
+        self._flush_grad_norms()
         if getattr(self, "_diag_on", False):
             self._flush_diagnostics()
         if _rank() == 0 and self.save_curves:
@@ -426,10 +455,45 @@ class Algo_PPO:
             self.diagnostics.append(entry)
         del self._pending_diag[:n]
 
+    def _queue_grad_norms(self):
+        """The iteration's gradient norms (update()'s device tensor) on their way to the host: an
+        asynchronous copy to pinned memory, appended by _flush_grad_norms once it has landed.  The
+        norms are the replicated, all-reduced gradients': equal on every rank, no collective."""
+        norms, names = self._norms_dev
+        self._norms_dev = None
+        if norms.device.type == "cuda":
+            host = torch.empty(norms.shape, dtype=torch.float64, pin_memory=True)
+            host.copy_(norms, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(norms.device))
+        else:  # (CPU test doubles)
+            host, ev = norms.clone(), None
+        self._pending_norms.append((host, ev, int(self.total_loop), list(names)))
+
+    def _flush_grad_norms(self, keep_last=False):
+        """Append the grad_norms entries whose norms have been read back (train_epochs' layout:
+        column j head j's critic, column H + j its actor)."""
+        pend = getattr(self, "_pending_norms", None)
+        if not pend:
+            return
+        n = len(pend) - (1 if keep_last else 0)
+        for host, ev, it, names in pend[:n]:
+            if ev is not None:
+                ev.synchronize()
+            cols = host.t().tolist()
+            H = len(names)
+            entry = {"iteration": it}
+            for kind, off in (("actor", H), ("critic", 0)):
+                for j, name in enumerate(names):
+                    entry[f"{kind}_{name}"] = cols[off + j]
+            self.grad_norms.append(entry)
+        del pend[:n]
+
     def curves(self):
         """The reward curves with every pending entry appended: (cross, wait, choice, balance).
-        (Also lands every pending entry of self.diagnostics.)"""
+        (Also lands every pending entry of self.diagnostics and self.grad_norms.)"""
         self._flush_curves()
+        self._flush_grad_norms()
         if getattr(self, "_diag_on", False):
             self._flush_diagnostics()
         return self.ep_reward_cross, self.ep_reward_wait, self.ep_reward_choice, self.ep_scenario_balance

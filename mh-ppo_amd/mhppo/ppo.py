@@ -360,10 +360,14 @@ class Head:
         self.exact = bool(exact)
 
 
-def train_epoch(heads, bucket=None):
+def train_epoch(heads, bucket=None, max_grad_norm=None, norms_out=None):
     """One full-batch epoch of every head: critic passes -> ONE all-reduce of all heads'
     advantage sums -> actor passes -> ONE gradient all-reduce -> Adam.  Returns this rank's
-    (actor, critic) loss sums per head (float64 [1] tensors)."""
+    (actor, critic) loss sums per head (float64 [1] tensors).
+    max_grad_norm (opt-in, adam_clip_steps): every net's gradient is clipped to that norm before
+    its step.  The clip runs after the gradient all-reduce: the reduced gradient is replicated, so
+    every rank measures the same norm and no further collective is needed.  norms_out: float64
+    [2 H], receives the norms before clipping in the order (head 0's actor, head 0's critic, ...)."""
     H = len(heads)
     sums = torch.zeros(2 * H, 3, dtype=torch.float64, device=heads[0].obs.device)  # critic rows, actor rows
     crit = [k_mlp_train(KIND_CRITIC, h.critic, h.obs, h.ret, m_global=h.m, sums=sums[i], exact=h.exact)
@@ -388,7 +392,11 @@ def train_epoch(heads, bucket=None):
         bucket.allreduce(nets)
     else:
         _allreduce_net_grads(*nets)
-    adam_steps([o for h in heads for o in (h.opt_actor, h.opt_critic)])
+    opts = [o for h in heads for o in (h.opt_actor, h.opt_critic)]
+    if max_grad_norm is None:
+        adam_steps(opts)
+    else:
+        adam_steps(opts, max_grad_norm, norms_out)
     return out
 
 
@@ -502,7 +510,7 @@ def _side_streams(dev, n):
     return _SIDE_STREAMS[key]
 
 
-def train_epochs(heads, n_epochs, bucket=None):
+def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None):
     """n_epochs full-batch epochs of every head, run as a pipeline of n_epochs + 1 steps: step k
     runs the actor passes of epoch k - 1 and the critic passes of epoch k (a continuous head on the
     split-precision kernel: ONE fused launch, mhppo_mlp_train_pair), then one gradient all-reduce
@@ -515,8 +523,18 @@ def train_epochs(heads, n_epochs, bucket=None):
     (_HeadPlan); an empty head (M == 0) runs k_mlp_train's empty-shard path.
     The float64 sums of all steps are one tensor [n_epochs + 1, 2 H, 3] (one fill, not one per
     step), and without data parallelism a head's advantage sums are read where its critic pass
-    left them (all_sums[k - 1, i, 1:3], two contiguous doubles: no copy)."""
+    left them (all_sums[k - 1, i, 1:3], two contiguous doubles: no copy).
+    max_grad_norm (opt-in, adam_clip_steps): every step's gradients are clipped to that norm per
+    net, after the gradient all-reduce (the reduced gradient is replicated: every rank measures the
+    same norm, no collective), and the call returns (losses, norms): norms float64 [n_epochs, 2 H]
+    on the device, norms[e, j] the norm before clipping of head j's critic at its epoch e,
+    norms[e, H + j] of head j's actor; NaN where a net was not stepped.  The launches fill it in
+    place, without a host read: step k's nets are (actors of epoch k - 1, critics of epoch k),
+    which in this layout are 2 H consecutive doubles starting at row k - 1, column H."""
     H = len(heads)
+    norms = None
+    if max_grad_norm is not None:
+        norms = torch.full((n_epochs, 2 * H), math.nan, dtype=torch.float64, device=heads[0].obs.device)
     dev = heads[0].obs.device
     all_sums = torch.zeros(n_epochs + 1, 2 * H, 3, dtype=torch.float64, device=dev)
     dp = _dp()
@@ -581,9 +599,16 @@ def train_epochs(heads, n_epochs, bucket=None):
             bucket.allreduce(trained)
         else:
             _allreduce_net_grads(*trained)
-        adam_steps([h.opt_actor for h in heads if h.actor in trained] +
-                   [h.opt_critic for h in heads if h.critic in trained])
+        opts = ([h.opt_actor for h in heads if h.actor in trained] +
+                [h.opt_critic for h in heads if h.critic in trained])
+        if norms is None:
+            adam_steps(opts)
+        elif opts:  # all H actors (k > 0), then all H critics (k < n_epochs)
+            off = (k - 1) * 2 * H + H if k > 0 else 0
+            adam_steps(opts, max_grad_norm, norms.view(-1)[off:off + len(opts)])
     del plans
+    if norms is not None:
+        return [tuple(o) for o in out], norms
     return [tuple(o) for o in out]
 
 
@@ -633,8 +658,12 @@ def _group_keys(opts):
 _ADAM_PLANS = {}
 
 
-def adam_steps(opts):
-    """One step of every optimiser in `opts`, bit-identical to calling o.step() on each.  For
+def adam_steps(opts, max_grad_norm=None, norms_out=None):
+    """One step of every optimiser in `opts`.  max_grad_norm set (opt-in): every net's gradient is
+    clipped to that norm first and the step runs on the native clip-and-Adam launch
+    (adam_clip_steps below; norms_out as there); the rest of this text is the default, None.
+
+    Bit-identical to calling o.step() on each.  For
     fused torch Adams (the GPU path) whose state exists, the steps of all six nets run as ONE
     step-count increment and one torch._fused_adam_ launch per distinct hyper-parameter set —
     the same per-tensor kernel arithmetic as each optimiser's own step (torch.optim.adam
@@ -646,6 +675,8 @@ def adam_steps(opts):
     step-order bookkeeping).  The grouped tensor lists are built once per optimiser set and
     reused (_AdamPlan: ~0.2 ms of host time per call otherwise).  Pinned by
     test_adam_steps_bit_identical_to_per_optimizer_steps."""
+    if max_grad_norm is not None:
+        return adam_clip_steps(opts, max_grad_norm, norms_out)
     key = tuple(id(o) for o in opts)
     plan = _ADAM_PLANS.get(key)
     if plan is not None and plan.opts == list(opts) and plan.valid(opts):
@@ -695,6 +726,258 @@ def _run_adam_plan(plan):
     for (_, lr, b1, b2, wd, eps, maximize), (ps, gs, ms, vs, sts) in plan.groups.items():
         torch._fused_adam_(ps, gs, ms, vs, [], sts, amsgrad=False, lr=lr, beta1=b1, beta2=b2, weight_decay=wd,
                            eps=eps, maximize=maximize, grad_scale=None, found_inf=None)
+
+
+# ------------------------------------------------- gradient-norm clipping + Adam (opt-in)
+# mhppo_adam_clip (include/mhppo.h, csrc/adam_clip.hip): per net the gradient norm in the fixed
+# fold order, the clip scale and the Adam step on the torch optimiser's own state, all nets of a
+# pipeline step in one launch.  adam_clip_torch is the contract's executable specification (the
+# tests compare the kernel with it bit for bit) and the CPU path.
+
+def fold_1024_4(x):
+    """The fold of a float64 vector in k_fold<1024, 4>'s order (csrc/block_prims.h): thread b's
+    chain u adds elements b + 1024 u (+ 4096 k) from +0.0, (a0 + a1) + (a2 + a3), the halving tree."""
+    x = x.reshape(-1)
+    n = x.numel()
+    rounds = max(1, -(-n // 4096))
+    pad = x.new_zeros(rounds * 4096)  # an absent element adds +0.0 to a chain that is never -0.0
+    pad[:n] = x
+    pad = pad.view(rounds, 4, 1024)
+    acc = x.new_zeros(4, 1024)
+    for r in range(rounds):
+        acc = acc + pad[r]
+    v = (acc[0] + acc[1]) + (acc[2] + acc[3])
+    s = 512
+    while s:
+        v = v[:s] + v[s:2 * s]
+        s //= 2
+    return v[0]
+
+
+def adam_clip_sumsq(grads):
+    """ss of the contract: the squares of the net's flat gradient (the tensors of `grads` in
+    order), exact in float64, folded in k_fold<1024, 4>'s order.  A float64 scalar tensor."""
+    g = torch.cat([x.detach().reshape(-1) for x in grads]).double()
+    return fold_1024_4(g * g)
+
+
+def _f32(x):
+    return torch.tensor(float(x), dtype=torch.float64).to(torch.float32)
+
+
+def adam_clip_torch(segs, t, lr, beta1, beta2, eps, max_norm, norm=None):
+    """mhppo_adam_clip's arithmetic for one net, operation for operation (include/mhppo.h), in
+    place on torch tensors: segs = [(param, grad, exp_avg, exp_avg_sq, step)] in flat order, t the
+    step count after the increment.  Returns the float64 norm before clipping (a Python float).
+    norm: use this value instead of sqrt(ss) (the tests feed the kernel's reported norm, so that a
+    last-bit difference of the float64 square root cannot move the comparison of the step)."""
+    if norm is None:
+        norm = math.sqrt(float(adam_clip_sumsq([s[1] for s in segs])))
+    coef = float(max_norm) / (norm + 1e-6)
+    s = _f32(coef) if coef < 1.0 else _f32(1.0)
+    a, q = _f32(lr / (1.0 - beta1 ** t)), _f32(math.sqrt(1.0 - beta2 ** t))
+    c1, b2, c2, e = _f32(1.0 - beta1), _f32(beta2), _f32(1.0 - beta2), _f32(eps)
+    with torch.no_grad():
+        for p, g, m, v, step in segs:
+            p, g = p.detach(), g.detach()
+            dev = p.device
+            gs = g * s.to(dev)
+            m.add_((gs - m) * c1.to(dev))
+            v.mul_(b2.to(dev)).add_((gs * gs) * c2.to(dev))
+            # sqrtf, correctly rounded: through float64 (a float32 root is never near enough to a
+            # rounding boundary for the second rounding to matter); torch's float32 CPU sqrt is a
+            # vectorised approximation that misses the IEEE result in ~0.6 % of the elements
+            den = (v.double().sqrt().float() / q.to(dev)) + e.to(dev)
+            p.sub_((m / den) * a.to(dev))
+            step.fill_(float(t))
+    return norm
+
+
+def _clip_group_ok(g):
+    return (not g.get("amsgrad") and not g.get("maximize") and not g.get("capturable")
+            and not g.get("differentiable") and not isinstance(g["lr"], torch.Tensor)
+            and float(g["weight_decay"]) == 0.0)
+
+
+class _ClipNet:
+    """One torch.optim.Adam as one net of a mhppo_adam_clip call: its parameters in order as the
+    segments, the state tensors' addresses and the host-side step count t.  t is read from the
+    state ONCE, when the record is built, and incremented per step; the record is rebuilt (and t
+    read again) when the optimiser's `state` or `param_groups` object, a state dict, a parameter's
+    storage or a `.grad` tensor is replaced (load_state_dict, .to(), zero_grad(set_to_none=True))
+    or a step hook appears.  What it cannot see is a step taken behind its back on the same state
+    objects (o.step(), adam_steps without max_grad_norm): clip_forget(opts) drops the records then.
+    ok is False for an optimiser the kernel does not serve (see adam_clip_steps)."""
+
+    def __init__(self, o):
+        self.opt, self.state, self.pg = o, o.state, o.param_groups
+        self.ok = False
+        if not (isinstance(o, torch.optim.Adam) and _no_step_hooks(o) and len(o.param_groups) == 1
+                and getattr(o, "grad_scale", None) is None and getattr(o, "found_inf", None) is None
+                and _clip_group_ok(o.param_groups[0])):
+            return
+        g = o.param_groups[0]
+        ps = [p for p in g["params"] if p.grad is not None]
+        if not ps or len(ps) > _lib.ADAM_MAX_SEGS:
+            return
+        dev = ps[0].device
+        if dev.type not in ("cuda", "cpu") or (dev.type == "cuda" and not g.get("fused")):
+            return  # a foreach / single-tensor GPU optimiser keeps `step` on the host
+        for p in ps:
+            if (p.dtype != torch.float32 or p.device != dev or not p.is_contiguous() or p.grad.dtype != torch.float32
+                    or p.grad.device != dev or not p.grad.is_contiguous()):
+                return
+        fresh = [p for p in ps if len(o.state[p]) == 0]
+        for p in fresh:  # the state torch's Adam._init_group would create at the first step
+            st = o.state[p]
+            st["step"] = (torch.zeros((), dtype=torch.float32, device=dev) if g.get("fused")
+                          else torch.tensor(0.0, dtype=torch.float32))
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        sts = [o.state[p] for p in ps]
+        for p, st in zip(ps, sts):
+            m, v, step = st.get("exp_avg"), st.get("exp_avg_sq"), st.get("step")
+            if not (torch.is_tensor(m) and torch.is_tensor(v) and torch.is_tensor(step)) or step.numel() != 1:
+                return
+            if step.dtype != torch.float32 or (dev.type == "cuda" and step.device != dev):
+                return
+            for x in (m, v):
+                if x.dtype != torch.float32 or x.device != dev or not x.is_contiguous() or x.numel() != p.numel():
+                    return
+        if len(fresh) == len(ps):
+            ts = {0}
+        else:  # one host read per optimiser and record
+            ts = {int(x) for x in torch.stack([st["step"].reshape(()).to(dev) for st in sts]).tolist()}
+        if len(ts) != 1:
+            return
+        self.t = ts.pop()
+        self.dev = dev
+        self.params = [(p, p.grad, p.data_ptr(), st) for p, st in zip(ps, sts)]
+        self.segs = [(p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["step"]) for p, st in zip(ps, sts)]
+        self.ok = True
+
+    def valid(self):
+        o = self.opt
+        if o.state is not self.state or o.param_groups is not self.pg or not _no_step_hooks(o):
+            return False
+        if not self.ok:
+            return False  # an unsupported optimiser is looked at again at every call
+        get = self.state.get
+        return _clip_group_ok(self.pg[0]) and all(p.grad is g and p.data_ptr() == ptr and get(p) is st
+                                                  for p, g, ptr, st in self.params)
+
+    def hyper(self):
+        """(t, lr, beta1, beta2, eps) of the step about to run: read at every call."""
+        g = self.pg[0]
+        return self.t + 1, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+
+
+_CLIP_NETS = {}    # id(optimiser) -> _ClipNet
+_CLIP_PLANS = {}   # ids of an optimiser set -> (records, ctypes table)
+
+
+def clip_forget(opts=None):
+    """Drop the clip path's records of `opts` (default: all), so the next clipped step reads the
+    step counts from the optimisers' state again."""
+    for k in ([id(o) for o in opts] if opts is not None else list(_CLIP_NETS)):
+        _CLIP_NETS.pop(k, None)
+    _CLIP_PLANS.clear()
+
+
+def _clip_net(o):
+    rec = _CLIP_NETS.get(id(o))
+    if rec is None or rec.opt is not o or not rec.valid():
+        if len(_CLIP_NETS) > 256:
+            clip_forget()
+        rec = _CLIP_NETS[id(o)] = _ClipNet(o)
+    return rec
+
+
+def _clip_table(recs):
+    nets = (_lib.AdamNet * len(recs))()
+    for net, rec in zip(nets, recs):
+        net.n_seg = len(rec.segs)
+        for sg, (p, g, m, v, step) in zip(net.seg, rec.segs):
+            sg.param, sg.grad, sg.exp_avg, sg.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+            sg.step, sg.n = step.data_ptr(), p.numel()
+    return nets
+
+
+def _clip_launch(recs, nets, max_norm, norms):
+    """One mhppo_adam_clip call for `recs` (all on one GPU) on the current stream."""
+    hs = [rec.hyper() for rec in recs]
+    for net, (t, lr, b1, b2, eps) in zip(nets, hs):
+        net.t, net.alpha, net.bias2 = t, lr / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t)
+        net.beta1, net.beta2, net.eps = b1, b2, eps
+    dev = recs[0].dev
+    with (contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)):
+        _lib.adam_clip(nets, len(recs), max_norm, norms.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    for rec in recs:
+        rec.t += 1
+
+
+def adam_clip_steps(opts, max_grad_norm, norms_out=None):
+    """adam_steps with the knob set: per optimiser (= per net) clip the gradient to max_grad_norm
+    (> 0; inf clips nothing and only measures), then one Adam step.  Returns the float64 norms
+    before clipping, one per optimiser in order, in norms_out (float64, contiguous,
+    len(opts) elements, on the nets' device) or a new tensor; nothing is read back to the host.
+
+    GPU: ONE mhppo_adam_clip launch for all optimisers of the call (include/mhppo.h has the
+    arithmetic), on the optimisers' own state tensors: state_dict() and the checkpoints stay the
+    truth.  The first step is native too: where torch has not created the Adam state yet it is
+    created here as Adam._init_group would (zero moments, a float32 device scalar `step`).  The
+    segment table is built once per optimiser set and reused under _AdamPlan's rule (identity of
+    state / param_groups / .grad, plus the parameters' addresses; _ClipNet says what rebuilds it
+    and what the host-side step count cannot see); lr, betas and eps are read at every call, so a
+    scheduler's changes apply.  CPU tensors (the test doubles) take adam_clip_torch, the same
+    arithmetic: CPU and GPU runs of one seed agree bit for bit in the optimiser.
+    Fallback: an optimiser the kernel does not serve (not torch.optim.Adam, weight_decay, amsgrad,
+    maximize, capturable, differentiable, a tensor lr, several param groups, more than 8 parameter
+    tensors, non-float32 or non-contiguous tensors, a GPU optimiser that is not fused=True (its
+    `step` lives on the host), step hooks) takes torch.nn.utils.clip_grad_norm_ on its
+    parameters, then o.step(); the others of the call still go native, one launch each."""
+    max_norm = float(max_grad_norm)
+    if not max_norm > 0.0:
+        raise ValueError(f"max_grad_norm must be > 0 (inf allowed), not {max_grad_norm!r}")
+    opts = list(opts)
+    if not opts:
+        return norms_out
+    key = tuple(id(o) for o in opts)
+    plan = _CLIP_PLANS.get(key)
+    if plan is not None and all(_CLIP_NETS.get(k) is rec and rec.valid() for k, rec in zip(key, plan[0])):
+        recs, nets = plan
+    else:
+        recs, nets = [_clip_net(o) for o in opts], None
+        _CLIP_PLANS.pop(key, None)
+    dev = recs[0].dev if recs[0].ok else next((p.device for p in opts[0].param_groups[0]["params"]), None)
+    if norms_out is None:
+        norms_out = torch.empty(len(opts), dtype=torch.float64, device=dev)
+    elif norms_out.dtype != torch.float64 or not norms_out.is_contiguous() or norms_out.numel() != len(opts):
+        raise ValueError("norms_out must be a contiguous float64 tensor with one element per optimiser")
+    if all(r.ok and r.dev.type == "cuda" and r.dev == dev for r in recs) and norms_out.device == dev:
+        if nets is None:
+            nets = _clip_table(recs)
+            if len(_CLIP_PLANS) > 64:
+                _CLIP_PLANS.clear()
+            _CLIP_PLANS[key] = (recs, nets)
+        _clip_launch(recs, nets, max_norm, norms_out)
+        return norms_out
+    for k, (o, rec) in enumerate(zip(opts, recs)):
+        if rec.ok and rec.dev.type == "cuda":
+            one = norms_out[k:k + 1] if norms_out.device == rec.dev else torch.empty(1, dtype=torch.float64,
+                                                                                     device=rec.dev)
+            _clip_launch([rec], _clip_table([rec]), max_norm, one)
+            if one.device != norms_out.device:
+                norms_out[k:k + 1].copy_(one)
+        elif rec.ok:
+            t, lr, b1, b2, eps = rec.hyper()
+            norms_out[k] = adam_clip_torch(rec.segs, t, lr, b1, b2, eps, max_norm)
+            rec.t += 1
+        else:
+            ps = [p for g in o.param_groups for p in g["params"] if p.grad is not None]
+            norms_out[k] = torch.nn.utils.clip_grad_norm_(ps, max_norm).detach().double()
+            o.step()
+    return norms_out
 
 
 def train_model_c(actor, critic, opt_actor, opt_critic, obs, act, logp_old, ret, m_global, exact=False):
