@@ -9,7 +9,7 @@
 #include "common.h"
 #include "launch1d.h"
 #include "libm_glibc.h"
-#include "ppo_math.h"  // philox
+#include "ppo_math.h"  // philox_draw
 
 using namespace mhppo;
 
@@ -18,16 +18,7 @@ namespace {
 __global__ void __launch_bounds__(TPB) k_philox(uint64_t seed, uint64_t off, float *out, int64_t n, int normal) {
   int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  uint64_t ctr = off + (uint64_t)i;
-  uint32_t c4[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x6d687070u, 0u};
-  philox(c4, (uint32_t)seed, (uint32_t)(seed >> 32));
-  if (normal) {
-    float u1 = ((float)(c4[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
-    float u2 = (float)(c4[1] >> 8) * (1.0f / 16777216.0f);
-    out[i] = sqrtf(-2.0f * logf(u1)) * cosf(6.2831853071795865f * u2);
-  } else {
-    out[i] = (float)(c4[0] >> 8) * (1.0f / 16777216.0f);
-  }
+  out[i] = philox_draw(seed, off + (uint64_t)i, normal != 0);
 }
 
 // The policy heads' glibc-exact transcendentals (libm_glibc.h) over float bit patterns
@@ -47,11 +38,7 @@ __global__ void __launch_bounds__(TPB) k_philox_normal_2d(uint64_t seed, uint64_
   if (i >= rows * cols) return;
   const int64_t r = i / cols, cc = i - r * cols;
   const uint64_t ctr = off + (uint64_t)r * stride + (uint64_t)cc;
-  uint32_t c4[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x6d687070u, 0u};
-  philox(c4, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const float u1 = ((float)(c4[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
-  const float u2 = (float)(c4[1] >> 8) * (1.0f / 16777216.0f);
-  out[i] = sqrtf(-2.0f * logf(u1)) * cosf(6.2831853071795865f * u2);
+  out[i] = philox_draw(seed, ctr, true);
 }
 
 }  // namespace

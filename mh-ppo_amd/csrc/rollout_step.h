@@ -99,7 +99,7 @@ __device__ __forceinline__ void sample_env_body(EV &E, const float *__restrict__
     }
     if (loc != loc && B.status) atomicOr(B.status, 2u);  // MultivariateNormal raises on a NaN loc
     float z = eps[(size_t)e * S + i];
-    float a = loc + MVN_L * z;
+    float a = mvn_sample(loc, z);
     rix[i] = !rec_of ? (int64_t)e * S + i
                        : (((emask >> i) & 1u) ? rbase + __builtin_popcount(emask & ((1u << i) - 1u)) : -1);
     const int64_t bt = (int64_t)t * c.N * S + rix[i];  // time-major records [T][N S]

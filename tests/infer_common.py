@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_INS = (5, 13, 27, 54, 64)
 KINDS = (0, 1, 2)
 MEAN, STD = -1.0, 3.0
-# csrc/ppo_math.h LN_0_8 / LN_1_2: float64 log(0.8), log(1.2)
-LN_0_8, LN_1_2 = float.fromhex("-0x1.c8ff7c79a9a20p-3"), float.fromhex("0x1.7565011e49675p-3")
+# csrc/ppo_math.h LN_0_8 / LN_1_2: the doubles d at which the float64 exp(d) reaches 0.8 / leaves 1.2
+LN_0_8, LN_1_2 = float.fromhex("-0x1.c8ff7c79a9a22p-3"), float.fromhex("0x1.7565011e49678p-3")
 MVN_L = np.float32(math.sqrt(0.5))
 
 
