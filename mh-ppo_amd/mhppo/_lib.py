@@ -193,7 +193,7 @@ def eval_stats_fold(env, state, sums, stream):
 
 
 def adam_clip(nets, n_nets, max_norm, norms, stream):
-    """mhppo_adam_clip, checked: the one place the entry point is called from (mhppo.ppo.adam_steps
+    """mhppo_adam_clip, checked: the one place the entry point is called from (mhppo.adam.adam_steps
     with max_grad_norm set), so a run with the knob off can be shown never to reach it.  `nets`: a
     ctypes array of AdamNet (host), `norms` / `stream`: addresses."""
     return check(lib().mhppo_adam_clip(ctypes.addressof(nets), n_nets, max_norm, norms, stream))

@@ -36,6 +36,33 @@ def _venv(env):
     return env.venv if hasattr(env, "venv") else env
 
 
+# The asynchronous read-backs of train() (reward-curve sums, diagnostics sums, gradient norms): an
+# iteration queues (host copy, event, *payload) without a host sync, and the entry is appended to
+# its list once the copy has landed, one iteration later or when curves() / the end of train() asks.
+def _readback(t, *payload):
+    """Queue entry for device tensor `t`: on the GPU a non-blocking copy to pinned memory and an
+    event on the current stream; on the CPU (test doubles: tests/test_dp_gloo.py) a clone, no event."""
+    if t.device.type == "cuda":
+        host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        host.copy_(t, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(t.device))
+    else:
+        host, ev = t.clone(), None
+    return (host, ev, *payload)
+
+
+def _land(queue, append, keep_last=False):
+    """append(host, *payload) for every entry of `queue` (keep_last: all but the newest, whose copy
+    may still be in flight), waiting for its event; the entries leave the queue."""
+    n = len(queue) - (1 if keep_last else 0)
+    for host, ev, *payload in queue[:n]:
+        if ev is not None:
+            ev.synchronize()
+        append(host, *payload)
+    del queue[:n]
+
+
 class Env_rollout:
     """Batched Env_rollout (:96-684): collects one episode per env per call."""
 
@@ -239,7 +266,7 @@ class Algo_PPO:
         # gradient-norm clipping (beyond the reference, whose steps are unbounded): None = off, the
         # iteration runs exactly the code it always did; a float > 0 clips every net's gradient to
         # that norm before each of its Adam steps, the first included, on the native clip-and-Adam
-        # launch (mhppo.ppo.adam_clip_steps); inf clips nothing and only records the norms
+        # launch (mhppo.adam.adam_clip_steps); inf clips nothing and only records the norms
         # (self.grad_norms).  A constructor argument, as gae_lambda is: nothing of it is checkpointed.
         self.max_grad_norm = None
         for k, v in hyperparameters.items():
@@ -259,9 +286,10 @@ class Algo_PPO:
 
     def update(self):
         """10 epochs of cross+wait, then 10 epochs of choice (:868-882) on the collected batch,
-        run as 10 joint epochs of the three independent heads (mhppo.ppo.train_epoch: same
-        results, two collectives per epoch under data parallelism).  The global row counts
-        and choice action counts take one all-reduce and one host sync per iteration."""
+        run as 10 joint epochs of the three independent heads in one pipeline of 11 steps
+        (mhppo.ppo.train_epochs: same results, two collectives per step under data parallelism).
+        The global row counts and choice action counts take one all-reduce and one host sync per
+        iteration."""
         r = self.rollout
         dev = self.venv.device
         c, w, d = r.cross, r.wait, r.choice
@@ -278,21 +306,16 @@ class Algo_PPO:
             else:  # the local counts are the global ones, known on the host: no sync
                 m_c, m_w, m_d = float(c["ret"].numel()), float(w["ret"].numel()), float(d["ret"].numel())
             heads, names = [], []
-            if m_c > 0:  # the reference trains a continuous head only on a non-empty batch (:869, :874)
-                heads.append(ppo.Head("c", self.actor_net_cross, self.critic_net_cross, self.optimizer_actor_cross,
-                                      self.optimizer_critic_cross, c["obs"], c["act"], c["logp"], c["ret"], m_c,
-                                      exact=self.exact_f32))
-                names.append("cross")
-            if m_w > 0:
-                heads.append(ppo.Head("c", self.actor_net_wait, self.critic_net_wait, self.optimizer_actor_wait,
-                                      self.optimizer_critic_wait, w["obs"], w["act"], w["logp"], w["ret"], m_w,
-                                      exact=self.exact_f32))
-                names.append("wait")
-            if m_d > 0:  # never empty in the reference (>= 1 existing car per episode); it would raise there
-                heads.append(ppo.Head("d", self.actor_net_choice, self.critic_net_choice, self.optimizer_actor_choice,
-                                      self.optimizer_critic_choice, d["obs"], d["act"], d["logp"], d["ret"], m_d,
-                                      counts, per_row=self.fix_choice_loss, exact=self.exact_f32))
-                names.append("choice")
+            # the reference trains a continuous head only on a non-empty batch (:869, :874); its choice
+            # batch is never empty (>= 1 existing car per episode; it would raise there)
+            for name, kind, b, m in (("cross", "c", c, m_c), ("wait", "c", w, m_w), ("choice", "d", d, m_d)):
+                if m > 0:
+                    heads.append(ppo.Head(kind, getattr(self, f"actor_net_{name}"), getattr(self, f"critic_net_{name}"),
+                                          getattr(self, f"optimizer_actor_{name}"),
+                                          getattr(self, f"optimizer_critic_{name}"), b["obs"], b["act"], b["logp"],
+                                          b["ret"], m, counts if kind == "d" else None,
+                                          per_row=kind == "d" and self.fix_choice_loss, exact=self.exact_f32))
+                    names.append(name)
             clip = getattr(self, "max_grad_norm", None)
             if clip is None:
                 losses = ppo.train_epochs(heads, 10, self.grad_bucket) if heads else None
@@ -370,16 +393,8 @@ class Algo_PPO:
             elif ppo._dp():
                 sums = sums.clone()  # the all-reduce below is in place
             ppo._allreduce_(sums)
-            if dev.type == "cuda":
-                # the reward curves take the sums without a host sync here: an asynchronous copy to
-                # pinned memory, appended once it has landed (next iteration, or the end of train)
-                host = torch.empty(3, dtype=torch.float64, pin_memory=True)
-                host.copy_(sums, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                self._pending_curves.append((host, ev, m_c, m_w, m_d))
-            else:  # (CPU test doubles of the rollout: tests/test_dp_gloo.py)
-                self._pending_curves.append((sums.clone(), None, m_c, m_w, m_d))
+            # the reward curves take the sums without a host sync here
+            self._pending_curves.append(_readback(sums, m_c, m_w, m_d))
             if self.verbose:
                 self._flush_curves()
             if self.verbose and _rank() == 0:
@@ -391,46 +406,42 @@ class Algo_PPO:
                 print("Number Cross is ==> {} and Number Wait is ==> {} ".format(int(m_c), int(m_w)))
             self.rollout.reset()
             self.total_loop = self.total_loop + 1
-            if len(self._pending_curves) > 1:  # the previous iteration's sums landed long ago
-                self._flush_curves(keep_last=True)
-            if diag and len(self._pending_diag) > 1:
-                self._flush_diagnostics(keep_last=True)
-            if len(getattr(self, "_pending_norms", ())) > 1:
-                self._flush_grad_norms(keep_last=True)
-        self._flush_curves()
-        self._flush_grad_norms()
-        if getattr(self, "_diag_on", False):
-            self._flush_diagnostics()
+            self._land_pending(keep_last=True)  # the previous iteration's copies landed long ago
+        self._land_pending()
         if _rank() == 0 and self.save_curves:
             self.save_reward_curves()
         if self.verbose and _rank() == 0:
             print("Complete")
 
-    def _flush_curves(self, keep_last=False):
-        """Append the reward-curve entries (rew_batch.mean() over the global batch, :886-892) of
-        the iterations whose reward sums have been read back."""
-        n = len(self._pending_curves) - (1 if keep_last else 0)
-        for host, ev, m_c, m_w, m_d in self._pending_curves[:n]:
-            if ev is not None:
-                ev.synchronize()
-            s = host.tolist()
-            if m_c > 0:
-                self.ep_reward_cross.append(s[0] / m_c)
-            if m_w > 0:
-                self.ep_reward_wait.append(s[1] / m_w)
-            self.ep_reward_choice.append(s[2] / m_d if m_d > 0 else float("nan"))  # mean() of empty: NaN
-            self.ep_scenario_balance.append([int(m_c), int(m_w)])
-        del self._pending_curves[:n]
+    def _land_pending(self, keep_last=False):
+        """Land the queued read-backs of the reward curves, the gradient norms and the diagnostics
+        (keep_last: all but each queue's newest entry).  A queue an object lacks is empty."""
+        for name, append in (("_pending_curves", self._append_curves), ("_pending_norms", self._append_grad_norms),
+                             ("_pending_diag", self._append_diagnostics)):
+            _land(getattr(self, name, []), append, keep_last)
+
+    def _flush_curves(self):
+        _land(self._pending_curves, self._append_curves)
+
+    def _append_curves(self, host, m_c, m_w, m_d):
+        """One iteration's reward-curve entries (rew_batch.mean() over the global batch, :886-892)
+        from its read-back reward sums."""
+        s = host.tolist()
+        if m_c > 0:
+            self.ep_reward_cross.append(s[0] / m_c)
+        if m_w > 0:
+            self.ep_reward_wait.append(s[1] / m_w)
+        self.ep_reward_choice.append(s[2] / m_d if m_d > 0 else float("nan"))  # mean() of empty: NaN
+        self.ep_scenario_balance.append([int(m_c), int(m_w)])
 
     def _queue_diagnostics(self):
         """One diagnostics launch per head update() just trained (post-update nets, this
-        iteration's buckets), one all-reduce of the stacked sums under data parallelism, and an
-        asynchronous copy to pinned memory (appended by _flush_diagnostics once it has landed)."""
+        iteration's buckets), one all-reduce of the stacked sums under data parallelism, and their
+        read-back (appended by _append_diagnostics once it has landed)."""
         heads = self._diag_heads or []
         if not heads:
             return
-        dev = self.venv.device
-        with torch.cuda.device(dev):
+        with torch.cuda.device(self.venv.device):
             rows = []
             for name, h in heads:
                 h._diag_work = self._diag_work.get(name)
@@ -438,64 +449,38 @@ class Algo_PPO:
                 self._diag_work[name] = h._diag_work
             sums = torch.stack(rows)  # [H, DIAG_N]
             ppo._allreduce_(sums)
-            host = torch.empty(sums.shape, dtype=torch.float64, pin_memory=True)
-            host.copy_(sums, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-        self._pending_diag.append((host, ev, int(self.total_loop), [(name, h.m, h.kind) for name, h in heads]))
+            self._pending_diag.append(_readback(sums, int(self.total_loop),
+                                                [(name, h.m, h.kind) for name, h in heads]))
 
-    def _flush_diagnostics(self, keep_last=False):
-        """Append the diagnostics entries whose sums have been read back."""
-        n = len(self._pending_diag) - (1 if keep_last else 0)
-        for host, ev, it, heads in self._pending_diag[:n]:
-            ev.synchronize()
-            entry = {"iteration": it}
-            for row, (name, m, kind) in zip(host.tolist(), heads):
-                entry[name] = ppo.diag_stats(row, m, entropy=(kind == "d"))
-            self.diagnostics.append(entry)
-        del self._pending_diag[:n]
+    def _append_diagnostics(self, host, it, heads):
+        entry = {"iteration": it}
+        for row, (name, m, kind) in zip(host.tolist(), heads):
+            entry[name] = ppo.diag_stats(row, m, entropy=(kind == "d"))
+        self.diagnostics.append(entry)
 
     def _queue_grad_norms(self):
-        """The iteration's gradient norms (update()'s device tensor) on their way to the host: an
-        asynchronous copy to pinned memory, appended by _flush_grad_norms once it has landed.  The
-        norms are the replicated, all-reduced gradients': equal on every rank, no collective."""
+        """The iteration's gradient norms (update()'s device tensor) on their way to the host,
+        appended by _append_grad_norms once they have landed.  The norms are the replicated,
+        all-reduced gradients': equal on every rank, no collective."""
         norms, names = self._norms_dev
         self._norms_dev = None
-        if norms.device.type == "cuda":
-            host = torch.empty(norms.shape, dtype=torch.float64, pin_memory=True)
-            host.copy_(norms, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(norms.device))
-        else:  # (CPU test doubles)
-            host, ev = norms.clone(), None
-        self._pending_norms.append((host, ev, int(self.total_loop), list(names)))
+        self._pending_norms.append(_readback(norms, int(self.total_loop), list(names)))
 
-    def _flush_grad_norms(self, keep_last=False):
-        """Append the grad_norms entries whose norms have been read back (train_epochs' layout:
-        column j head j's critic, column H + j its actor)."""
-        pend = getattr(self, "_pending_norms", None)
-        if not pend:
-            return
-        n = len(pend) - (1 if keep_last else 0)
-        for host, ev, it, names in pend[:n]:
-            if ev is not None:
-                ev.synchronize()
-            cols = host.t().tolist()
-            H = len(names)
-            entry = {"iteration": it}
-            for kind, off in (("actor", H), ("critic", 0)):
-                for j, name in enumerate(names):
-                    entry[f"{kind}_{name}"] = cols[off + j]
-            self.grad_norms.append(entry)
-        del pend[:n]
+    def _append_grad_norms(self, host, it, names):
+        """One grad_norms entry (train_epochs' layout: column j head j's critic, column H + j its
+        actor)."""
+        cols = host.t().tolist()
+        H = len(names)
+        entry = {"iteration": it}
+        for kind, off in (("actor", H), ("critic", 0)):
+            for j, name in enumerate(names):
+                entry[f"{kind}_{name}"] = cols[off + j]
+        self.grad_norms.append(entry)
 
     def curves(self):
         """The reward curves with every pending entry appended: (cross, wait, choice, balance).
         (Also lands every pending entry of self.diagnostics and self.grad_norms.)"""
-        self._flush_curves()
-        self._flush_grad_norms()
-        if getattr(self, "_diag_on", False):
-            self._flush_diagnostics()
+        self._land_pending()
         return self.ep_reward_cross, self.ep_reward_wait, self.ep_reward_choice, self.ep_scenario_balance
 
     def _curve_path(self, name):

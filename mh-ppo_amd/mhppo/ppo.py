@@ -35,6 +35,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .adam import adam_clip_steps, adam_clip_sumsq, adam_clip_torch, adam_steps, clip_forget, fold_1024_4  # noqa: F401
 
 
 _FORCE_COLLECTIVES = False
@@ -205,50 +206,91 @@ def n_params(n_in, n_out):
     return 32 * n_in + 32 + 64 * 32 + 64 + 32 * 64 + 32 + 32 * n_out + n_out
 
 
+_MODEL_TYPE = {KIND_CRITIC: 0, KIND_CONT: 1, KIND_CHOICE: 2}  # the Model_PPO.model_type a pass kind trains
+
+
+def _check_net(kind, net, pair=False):
+    """The one net check of the train passes: `net` is what a pass of `kind` trains (pair: as one
+    of the two 13 -> 1 nets of the fused pair launch)."""
+    if pair:
+        if net.model_type != _MODEL_TYPE[kind] or net.n_in != 13 or net.n_out != 1:
+            raise ValueError("the fused pair launch trains a 13 -> 1 continuous actor and its 13 -> 1 critic")
+    elif net.model_type != _MODEL_TYPE[kind] or net.n_in > N_IN_MAX or (kind == KIND_CONT and net.n_in != 13):
+        raise ValueError(f"fused kernel kind {kind} cannot train a model_type {net.model_type} "
+                         f"{net.n_in}->{net.n_out} Model_PPO")
+
+
+def _obs_rows(obs):
+    """The observation rows as the kernels read them: float32, contiguous, 16-byte aligned."""
+    obs = obs.float().contiguous()
+    return obs.clone() if obs.data_ptr() % 16 else obs
+
+
+def _addr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _ev_begin():
+    if TRAIN_EVENTS is None:
+        return None
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    return ev
+
+
+def _ev_end(ev, kind, n_in, M):
+    if ev is not None:
+        ev[1].record()
+        TRAIN_EVENTS.append((kind, n_in, M, ev[0], ev[1]))
+
+
+# The raw launchers: the one call site of each C entry point.  Addresses (or None), sizes and the
+# hipStream_t handle; the caller has made the tensors' device current and keeps them alive.  The
+# launch events are recorded on the current stream, which the callers make the launch stream.
+def _launch_train(kind, flags, n_in, w, obs, M, ret, V, act, lp, stats, counts, m, mean, std, grad, sums, st):
+    ev = _ev_begin()
+    _lib.check(_lib.lib().mhppo_mlp_train(kind | flags, n_in, w, obs, M, ret, V, act, lp, stats, counts, m, mean, std,
+                                          grad, sums, st))
+    _ev_end(ev, kind, n_in, M)
+
+
+def _launch_pair(wa, wc, obs, M, ret, V, act, lp, stats, m, mean, std, ga, sums_a, gc, sums_c, st):
+    ev = _ev_begin()
+    _lib.check(_lib.lib().mhppo_mlp_train_pair(wa, wc, obs, M, ret, V, act, lp, stats, m, mean, std, ga, sums_a, gc,
+                                               sums_c, st))
+    _ev_end(ev, 3, 13, M)  # kind 3: a fused pair launch (two passes)
+
+
 def k_mlp_train(kind, net, obs, ret, value=None, act=None, logp_old=None, stats=None, counts=None, m_global=1.0,
                 exact=False, sums=None):
-    """Fused forward/loss/backward of one head (mhppo_mlp_train).
+    """Fused forward/loss/backward of one head (mhppo_mlp_train), one validated call: the tests'
+    and tools' entry (the update's drivers resolve a head's arguments once, _HeadPlan).
     kind 0 (critic): returns (grad, sums[3] = (sum (V-G)^2, sum A, sum A^2), V).
     kind 1 (continuous actor) / 2 (choice actor): returns (grad, sums[3] = (sum surrogate, 0, 0), None).
     grad is the packed torch-layout gradient (W1 b1 .. W4 b4), written into the net's flat
     .grad storage.  An empty `obs` (an empty data-parallel shard) gives a zero gradient.
-    `sums`: optional zeroed float64 [3] the kernel accumulates into (train_epoch passes rows of
-    one zeroed tensor: one fill per epoch instead of one per pass).
+    `sums`: optional zeroed float64 [3] the kernel accumulates into.
     exact: the f32-MFMA kernel instead of the split-precision one (any head with n_in <= 54;
     wider choice heads always run on f32 MFMA)."""
-    want = {KIND_CRITIC: 0, KIND_CONT: 1, KIND_CHOICE: 2}[kind]
-    if net.model_type != want or net.n_in > N_IN_MAX or (kind == KIND_CONT and net.n_in != 13):
-        raise ValueError(f"fused kernel kind {kind} cannot train a model_type {net.model_type} "
-                         f"{net.n_in}->{net.n_out} Model_PPO")
+    _check_net(kind, net)
     dev = obs.device
+    obs = _obs_rows(obs)
     M = obs.shape[0]
-    obs = obs.float().contiguous()
-    if obs.data_ptr() % 16:
-        obs = obs.clone()
     ret = ret.float().contiguous()
     V = torch.empty(M, dtype=torch.float32, device=dev) if kind == KIND_CRITIC else value.detach().float().contiguous()
     act = None if act is None else act.float().contiguous()
     logp_old = None if logp_old is None else logp_old.float().contiguous()
-    np_ = n_params(net.n_in, net.n_out)
     grad = net.grad_flat()
-    if grad.numel() != np_ or grad.device != dev:
+    if grad.numel() != n_params(net.n_in, net.n_out) or grad.device != dev:
         raise ValueError("gradient storage does not match the net / the batch's device")
     if sums is None:
         sums = torch.zeros(3, dtype=torch.float64, device=dev)
     w = net.flat()
-    p = _lib.ptr
-    ev = None
-    if TRAIN_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    flags = TRAIN_EXACT_F32 if exact else 0
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mhppo_mlp_train(
-            kind | flags, net.n_in, p(w), p(obs), M, p(ret), p(V), p(act), p(logp_old), p(stats), p(counts),
-            float(m_global), float(net.mean), float(net.std), p(grad), p(sums), _lib.stream_ptr()))
-    if ev is not None:
-        ev[1].record()
-        TRAIN_EVENTS.append((kind, net.n_in, M, ev[0], ev[1]))
+        _launch_train(kind, TRAIN_EXACT_F32 if exact else 0, net.n_in, w.data_ptr(), obs.data_ptr(), M, ret.data_ptr(),
+                      V.data_ptr(), _addr(act), _addr(logp_old), _addr(stats), _addr(counts), float(m_global),
+                      float(net.mean), float(net.std), grad.data_ptr(), sums.data_ptr(),
+                      torch.cuda.current_stream(dev).cuda_stream)
     return grad, sums, (V if kind == KIND_CRITIC else None)
 
 
@@ -258,31 +300,21 @@ def k_mlp_train_pair(actor, critic, obs, ret, value, act, logp_old, stats, m_glo
     with V_{e+1}; `stats` are the critic pass e's global advantage sums; the critic's weights
     must already carry its Adam step e.  Gradients go to both nets' flat .grad storage; the
     float64 sums accumulate into sums_actor / sums_critic (zeroed [3] each)."""
-    for net, kind in ((actor, 1), (critic, 0)):
-        if net.model_type != kind or net.n_in != 13 or net.n_out != 1:
-            raise ValueError("the fused pair launch trains a 13 -> 1 continuous actor and its 13 -> 1 critic")
+    _check_net(KIND_CONT, actor, pair=True)
+    _check_net(KIND_CRITIC, critic, pair=True)
     dev = obs.device
+    obs = _obs_rows(obs)
     M = obs.shape[0]
-    obs = obs.float().contiguous()
-    if obs.data_ptr() % 16:
-        obs = obs.clone()
     ret, act, logp_old = ret.float().contiguous(), act.float().contiguous(), logp_old.float().contiguous()
     if value.dtype != torch.float32 or not value.is_contiguous() or value.numel() != M:
         raise ValueError("value must be the float32 [M] buffer of the previous critic pass (updated in place)")
     ga, gc = actor.grad_flat(), critic.grad_flat()
-    p = _lib.ptr
-    ev = None
-    if TRAIN_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+    wa, wc = actor.flat(), critic.flat()
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mhppo_mlp_train_pair(
-            p(actor.flat()), p(critic.flat()), p(obs), M, p(ret), p(value), p(act), p(logp_old), p(stats),
-            float(m_global), float(actor.mean), float(actor.std), p(ga), p(sums_actor), p(gc), p(sums_critic),
-            _lib.stream_ptr()))
-    if ev is not None:
-        ev[1].record()
-        TRAIN_EVENTS.append((3, 13, M, ev[0], ev[1]))  # kind 3: a fused pair launch (two passes)
+        _launch_pair(wa.data_ptr(), wc.data_ptr(), obs.data_ptr(), M, ret.data_ptr(), value.data_ptr(), act.data_ptr(),
+                     logp_old.data_ptr(), _addr(stats), float(m_global), float(actor.mean), float(actor.std),
+                     ga.data_ptr(), sums_actor.data_ptr(), gc.data_ptr(), sums_critic.data_ptr(),
+                     torch.cuda.current_stream(dev).cuda_stream)
     return ga, gc, value
 
 
@@ -360,46 +392,6 @@ class Head:
         self.exact = bool(exact)
 
 
-def train_epoch(heads, bucket=None, max_grad_norm=None, norms_out=None):
-    """One full-batch epoch of every head: critic passes -> ONE all-reduce of all heads'
-    advantage sums -> actor passes -> ONE gradient all-reduce -> Adam.  Returns this rank's
-    (actor, critic) loss sums per head (float64 [1] tensors).
-    max_grad_norm (opt-in, adam_clip_steps): every net's gradient is clipped to that norm before
-    its step.  The clip runs after the gradient all-reduce: the reduced gradient is replicated, so
-    every rank measures the same norm and no further collective is needed.  norms_out: float64
-    [2 H], receives the norms before clipping in the order (head 0's actor, head 0's critic, ...)."""
-    H = len(heads)
-    sums = torch.zeros(2 * H, 3, dtype=torch.float64, device=heads[0].obs.device)  # critic rows, actor rows
-    crit = [k_mlp_train(KIND_CRITIC, h.critic, h.obs, h.ret, m_global=h.m, sums=sums[i], exact=h.exact)
-            for i, h in enumerate(heads)]
-    stats = sums[:H, 1:3].reshape(-1).contiguous()
-    _allreduce_(stats)
-    out = []
-    for i, (h, (_, sc, V)) in enumerate(zip(heads, crit)):
-        st = stats[2 * i:2 * i + 2]
-        sa = sums[H + i]
-        if h.kind == "c":
-            k_mlp_train(KIND_CONT, h.actor, h.obs, h.ret, V, h.act, h.logp, st, m_global=h.m, sums=sa, exact=h.exact)
-        elif h.per_row:
-            k_mlp_train(KIND_CHOICE, h.actor, h.obs, h.ret, V, h.act.float(), h.logp, st, None, m_global=h.m,
-                        sums=sa, exact=h.exact)
-        else:
-            k_mlp_train(KIND_CHOICE, h.actor, h.obs, h.ret, V, None, h.logp, st, h.counts, m_global=h.m, sums=sa,
-                        exact=h.exact)
-        out.append((sa[0:1], sc[0:1]))
-    nets = [n for h in heads for n in (h.actor, h.critic)]
-    if bucket is not None:
-        bucket.allreduce(nets)
-    else:
-        _allreduce_net_grads(*nets)
-    opts = [o for h in heads for o in (h.opt_actor, h.opt_critic)]
-    if max_grad_norm is None:
-        adam_steps(opts)
-    else:
-        adam_steps(opts, max_grad_norm, norms_out)
-    return out
-
-
 # Fuse each continuous head's actor pass e with its critic pass e + 1 (train_epochs) when the head
 # has at most PAIR_MAX_ROWS rows (global).  The fused launch shares one input load and saves a
 # launch, a weight-staging prologue and a reduction pair per epoch, but with two nets in one wave
@@ -418,75 +410,99 @@ def _use_pair(h):
 
 
 class _HeadPlan:
-    """One head's launch arguments for a whole train_epochs call, resolved once: the batch as
-    contiguous float32 (16-byte aligned rows), the nets' flat weight / gradient pointers (fixed
-    while the epochs run: the fused Adam updates them in place) and one V buffer.  Per pass only
-    the stats / sums pointers change — the Python cost of a pass is one ctypes call (the per-call
-    re-validation in k_mlp_train, ~60 us of host time, left the GPU idle on small batches)."""
+    """One head's launch arguments for a whole train_epoch / train_epochs call, resolved once: the
+    nets checked, the batch as contiguous float32 (16-byte aligned rows), the nets' flat weight /
+    gradient pointers (fixed while the epochs run: the fused Adam updates them in place) and one V
+    buffer.  Per pass only the stats / sums pointers change — the Python cost of a pass is one
+    ctypes call (a per-call validation as in k_mlp_train, ~60 us of host time, left the GPU idle
+    on small batches).  A head with no local rows (an empty data-parallel shard) has a plan too:
+    with M == 0 the entry points zero the gradient and touch nothing else (include/mhppo.h)."""
 
     def __init__(self, h):
-        for net, kind in ((h.critic, KIND_CRITIC), (h.actor, KIND_CONT if h.kind == "c" else KIND_CHOICE)):
-            want = {KIND_CRITIC: 0, KIND_CONT: 1, KIND_CHOICE: 2}[kind]
-            if net.model_type != want or net.n_in > N_IN_MAX or (kind == KIND_CONT and net.n_in != 13):
-                raise ValueError(f"fused kernel kind {kind} cannot train a model_type {net.model_type} "
-                                 f"{net.n_in}->{net.n_out} Model_PPO")
-        obs = h.obs.float().contiguous()
-        if obs.data_ptr() % 16:
-            obs = obs.clone()
-        self.obs, self.ret = obs, h.ret.float().contiguous()
-        self.M = obs.shape[0]
+        cont = h.kind == "c"
+        self.akind = KIND_CONT if cont else KIND_CHOICE
+        _check_net(KIND_CRITIC, h.critic)
+        _check_net(self.akind, h.actor)
+        self.obs, self.ret = _obs_rows(h.obs), h.ret.float().contiguous()
+        self.M = self.obs.shape[0]
         self.lp = h.logp.float().contiguous()
-        self.act = h.act.float().contiguous() if (h.kind == "c" or h.per_row) else None
-        self.counts = None if (h.kind == "c" or h.per_row) else h.counts
-        self.V = torch.empty(self.M, dtype=torch.float32, device=obs.device)
+        # a choice head passes its global counts, or with the per-row loss its actions: never both
+        self.act = h.act.float().contiguous() if (cont or h.per_row) else None
+        self.counts = None if (cont or h.per_row) else h.counts
+        self.V = torch.empty(self.M, dtype=torch.float32, device=self.obs.device)
         self.n_in = h.actor.n_in
-        self.wa, self.wc = h.actor.flat().data_ptr(), h.critic.flat().data_ptr()
+        self.keep = (h.actor.flat(), h.critic.flat())  # the storages the pointers below point into
+        self.wa, self.wc = self.keep[0].data_ptr(), self.keep[1].data_ptr()
         self.ga, self.gc = h.actor.grad_flat().data_ptr(), h.critic.grad_flat().data_ptr()
         self.mean, self.std = float(h.actor.mean), float(h.actor.std)
         self.flags = TRAIN_EXACT_F32 if h.exact else 0
-        self.akind = KIND_CONT if h.kind == "c" else KIND_CHOICE
-        self.keep = (h.actor.flat(), h.critic.flat())  # the storages the pointers above point into
+        # an empty shard's actor and critic passes stay two launches (the launch record's rows)
+        self.pair = _use_pair(h) and self.M > 0
+        self.x, self.r, self.v, self.l = (t.data_ptr() for t in (self.obs, self.ret, self.V, self.lp))
+        self.a, self.cn = _addr(self.act), _addr(self.counts)
 
 
-def _ev_begin():
-    if TRAIN_EVENTS is None:
-        return None
-    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    ev[0].record()
-    return ev
-
-
-def _ev_end(ev, kind, n_in, M):
-    if ev is not None:
-        ev[1].record()
-        TRAIN_EVENTS.append((kind, n_in, M, ev[0], ev[1]))
-
-
-# The three launch helpers of train_epochs (module-level so CPU test doubles can stand in for them:
-# tests/test_dp_gloo.py).  sums / stats are float64 views: [3] rows of the step's sums, [2] stats.
+# The three pass helpers of train_epoch / train_epochs, the only way the drivers reach the kernels
+# (module-level names looked up at call time, so CPU test doubles can stand in for them:
+# tests/test_dp_gloo.py).  sums / stats are float64 views: [3] rows of the step's sums, [2] stats;
+# st is the hipStream_t handle of the current stream.
 def _critic_pass(p, h, sums, st):
-    ev = _ev_begin()
-    _lib.check(_lib.lib().mhppo_mlp_train(
-        KIND_CRITIC | p.flags, p.n_in, p.wc, p.obs.data_ptr(), p.M, p.ret.data_ptr(), p.V.data_ptr(), None, None, None,
-        None, h.m, 0.0, 1.0, p.gc, sums.data_ptr(), st))
-    _ev_end(ev, KIND_CRITIC, p.n_in, p.M)
+    _launch_train(KIND_CRITIC, p.flags, p.n_in, p.wc, p.x, p.M, p.r, p.v, None, None, None, None, h.m, 0.0, 1.0, p.gc,
+                  sums.data_ptr(), st)
 
 
 def _actor_pass(p, h, stats, sums, st):
-    ev = _ev_begin()
-    _lib.check(_lib.lib().mhppo_mlp_train(
-        p.akind | p.flags, p.n_in, p.wa, p.obs.data_ptr(), p.M, p.ret.data_ptr(), p.V.data_ptr(),
-        None if p.act is None else p.act.data_ptr(), p.lp.data_ptr(), stats.data_ptr(),
-        None if p.counts is None else p.counts.data_ptr(), h.m, p.mean, p.std, p.ga, sums.data_ptr(), st))
-    _ev_end(ev, p.akind, p.n_in, p.M)
+    _launch_train(p.akind, p.flags, p.n_in, p.wa, p.x, p.M, p.r, p.v, p.a, p.l, stats.data_ptr(), p.cn, h.m, p.mean,
+                  p.std, p.ga, sums.data_ptr(), st)
 
 
 def _pair_pass(p, h, stats, sums_a, sums_c, st):
-    ev = _ev_begin()
-    _lib.check(_lib.lib().mhppo_mlp_train_pair(
-        p.wa, p.wc, p.obs.data_ptr(), p.M, p.ret.data_ptr(), p.V.data_ptr(), p.act.data_ptr(), p.lp.data_ptr(),
-        stats.data_ptr(), h.m, p.mean, p.std, p.ga, sums_a.data_ptr(), p.gc, sums_c.data_ptr(), st))
-    _ev_end(ev, 3, 13, p.M)  # kind 3: a fused pair launch (two passes)
+    _launch_pair(p.wa, p.wc, p.x, p.M, p.r, p.v, p.a, p.l, stats.data_ptr(), h.m, p.mean, p.std, p.ga,
+                 sums_a.data_ptr(), p.gc, sums_c.data_ptr(), st)
+
+
+def _on_device(dev):
+    return torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()
+
+
+def _reduce_and_step(nets, opts, bucket, max_grad_norm, norms_out):
+    """A step's epilogue: the gradient all-reduce of `nets` (in the bucket, or packed), then one
+    adam_steps call over `opts`, their optimisers in the driver's order, clipped when max_grad_norm
+    is set (norms_out: float64, contiguous, one element per optimiser, or None)."""
+    if bucket is not None:
+        bucket.allreduce(nets)
+    else:
+        _allreduce_net_grads(*nets)
+    if max_grad_norm is None:
+        adam_steps(opts)
+    elif opts:
+        adam_steps(opts, max_grad_norm, norms_out)
+
+
+def train_epoch(heads, bucket=None, max_grad_norm=None, norms_out=None):
+    """One full-batch epoch of every head: critic passes -> ONE all-reduce of all heads'
+    advantage sums -> actor passes -> ONE gradient all-reduce -> Adam.  Returns this rank's
+    (actor, critic) loss sums per head (float64 [1] tensors).  The sequential schedule
+    train_epochs' pipeline is compared with, on the same plans and pass helpers.
+    max_grad_norm (opt-in, adam_clip_steps): every net's gradient is clipped to that norm before
+    its step.  The clip runs after the gradient all-reduce: the reduced gradient is replicated, so
+    every rank measures the same norm and no further collective is needed.  norms_out: float64
+    [2 H], receives the norms before clipping in the order (head 0's actor, head 0's critic, ...)."""
+    H = len(heads)
+    dev = heads[0].obs.device
+    with _on_device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+        sums = torch.zeros(2 * H, 3, dtype=torch.float64, device=dev)  # critic rows, actor rows
+        plans = [_HeadPlan(h) for h in heads]
+        for i, (p, h) in enumerate(zip(plans, heads)):
+            _critic_pass(p, h, sums[i], st)
+        stats = sums[:H, 1:3].reshape(-1).contiguous()
+        _allreduce_(stats)
+        for i, (p, h) in enumerate(zip(plans, heads)):
+            _actor_pass(p, h, stats[2 * i:2 * i + 2], sums[H + i], st)
+        _reduce_and_step([n for h in heads for n in (h.actor, h.critic)],
+                         [o for h in heads for o in (h.opt_actor, h.opt_critic)], bucket, max_grad_norm, norms_out)
+    return [(sums[H + i, 0:1], sums[i, 0:1]) for i in range(H)]
 
 
 # Heads' passes on alternating streams within an epoch step (train_epochs): head i's passes on
@@ -520,7 +536,7 @@ def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None):
     of epoch e + 1 the critic's weights after its Adam step e; each optimiser steps n_epochs
     times.  Returns this rank's (actor, critic) loss sums of the last epoch per head.
     The launches go straight through the C-ABI with each head's arguments resolved once
-    (_HeadPlan); an empty head (M == 0) runs k_mlp_train's empty-shard path.
+    (_HeadPlan); an empty head (M == 0) runs the same passes, never paired: each zeroes a gradient.
     The float64 sums of all steps are one tensor [n_epochs + 1, 2 H, 3] (one fill, not one per
     step), and without data parallelism a head's advantage sums are read where its critic pass
     left them (all_sums[k - 1, i, 1:3], two contiguous doubles: no copy).
@@ -532,452 +548,68 @@ def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None):
     place, without a host read: step k's nets are (actors of epoch k - 1, critics of epoch k),
     which in this layout are 2 H consecutive doubles starting at row k - 1, column H."""
     H = len(heads)
-    norms = None
-    if max_grad_norm is not None:
-        norms = torch.full((n_epochs, 2 * H), math.nan, dtype=torch.float64, device=heads[0].obs.device)
     dev = heads[0].obs.device
-    all_sums = torch.zeros(n_epochs + 1, 2 * H, 3, dtype=torch.float64, device=dev)
-    dp = _dp()
-    paired = [_use_pair(h) for h in heads]
-    plans = [_HeadPlan(h) if h.obs.shape[0] > 0 else None for h in heads]
-    main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-    side = _side_streams(dev, min(TRAIN_STREAMS, H) - 1)
-    streams = [main] + side
-    stats = None        # all-reduced advantage sums of the previous step's critic passes [2H]
-    out = [[None, None] for _ in range(H)]
-    for k in range(n_epochs + 1):
-        sums = all_sums[k]  # critic rows, actor rows
-        crit = k < n_epochs
-        trained = []
-        if side:  # the side streams start after this step's inputs (Adam, sums, stats) on main
-            fork = torch.cuda.Event()
-            fork.record(main)
-            for sd in side:
-                sd.wait_event(fork)
-        for i, h in enumerate(heads):
-            p = plans[i]
-            sc, sa = sums[i], sums[H + i]
-            sti = streams[i % len(streams)]
-            ctx = torch.cuda.stream(sti) if sti is not None else contextlib.nullcontext()
-            st = sti.cuda_stream if sti is not None else None
-            with ctx:
-                stp = None
-                if k > 0:  # the previous step's critic pass sums (all-reduced under data parallelism)
-                    stp = stats[2 * i:2 * i + 2] if dp else all_sums[k - 1, i, 1:3]
-                if p is None:  # an empty shard: zero gradients, sums unchanged (k_mlp_train's M == 0 path)
-                    if k > 0:
-                        cont = h.kind == "c"
-                        k_mlp_train(KIND_CONT if cont else KIND_CHOICE, h.actor, h.obs, h.ret, h.obs.new_empty(0),
-                                    h.act if (cont or h.per_row) else None, h.logp, stp,
-                                    None if (cont or h.per_row) else h.counts, m_global=h.m, sums=sa, exact=h.exact)
-                        trained.append(h.actor)
-                        out[i][0] = sums[H + i, 0:1]
-                    if crit:
-                        k_mlp_train(KIND_CRITIC, h.critic, h.obs, h.ret, m_global=h.m, sums=sc, exact=h.exact)
-                        trained.append(h.critic)
-                        out[i][1] = sums[i, 0:1]
-                    continue
-                if k > 0 and crit and paired[i]:
-                    _pair_pass(p, h, stp, sa, sc, st)
-                    trained += [h.actor, h.critic]
-                    out[i] = [sums[H + i, 0:1], sums[i, 0:1]]
-                    continue
-                if k > 0:  # the actor pass of epoch k - 1
-                    _actor_pass(p, h, stp, sa, st)
+    with _on_device(dev):
+        norms = None
+        if max_grad_norm is not None:
+            norms = torch.full((n_epochs, 2 * H), math.nan, dtype=torch.float64, device=dev)
+        all_sums = torch.zeros(n_epochs + 1, 2 * H, 3, dtype=torch.float64, device=dev)
+        dp = _dp()
+        plans = [_HeadPlan(h) for h in heads]
+        main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+        side = _side_streams(dev, min(TRAIN_STREAMS, H) - 1)
+        streams = [main] + side
+        handles = [None if s is None else s.cuda_stream for s in streams]
+        same_stream = contextlib.nullcontext()
+        stats = None        # all-reduced advantage sums of the previous step's critic passes [2H]
+        out = [[None, None] for _ in range(H)]
+        for k in range(n_epochs + 1):
+            sums = all_sums[k]  # critic rows, actor rows
+            crit = k < n_epochs
+            trained = []
+            if side:  # the side streams start after this step's inputs (Adam, sums, stats) on main
+                fork = torch.cuda.Event()
+                fork.record(main)
+                for sd in side:
+                    sd.wait_event(fork)
+            for i, h in enumerate(heads):
+                p = plans[i]
+                sc, sa = sums[i], sums[H + i]
+                j = i % len(streams)
+                st = handles[j]
+                # (one stream: main is the current stream already; the launch events record on it)
+                with (torch.cuda.stream(streams[j]) if side else same_stream):
+                    stp = None
+                    if k > 0:  # the previous step's critic pass sums (all-reduced under data parallelism)
+                        stp = stats[2 * i:2 * i + 2] if dp else all_sums[k - 1, i, 1:3]
+                    if k > 0 and crit and p.pair:
+                        _pair_pass(p, h, stp, sa, sc, st)
+                    else:
+                        if k > 0:  # the actor pass of epoch k - 1
+                            _actor_pass(p, h, stp, sa, st)
+                        if crit:  # the critic pass of epoch k
+                            _critic_pass(p, h, sc, st)
+                if k > 0:
                     trained.append(h.actor)
                     out[i][0] = sums[H + i, 0:1]
-                if crit:  # the critic pass of epoch k
-                    _critic_pass(p, h, sc, st)
+                if crit:
                     trained.append(h.critic)
                     out[i][1] = sums[i, 0:1]
-        for sd in side:  # join
-            main.wait_stream(sd)
-        if crit and dp:  # the all-reduce needs one span
-            stats = sums[:H, 1:3].reshape(-1).contiguous()
-            _allreduce_(stats)
-        if bucket is not None:
-            bucket.allreduce(trained)
-        else:
-            _allreduce_net_grads(*trained)
-        opts = ([h.opt_actor for h in heads if h.actor in trained] +
-                [h.opt_critic for h in heads if h.critic in trained])
-        if norms is None:
-            adam_steps(opts)
-        elif opts:  # all H actors (k > 0), then all H critics (k < n_epochs)
-            off = (k - 1) * 2 * H + H if k > 0 else 0
-            adam_steps(opts, max_grad_norm, norms.view(-1)[off:off + len(opts)])
-    del plans
+            for sd in side:  # join
+                main.wait_stream(sd)
+            if crit and dp:  # the all-reduce needs one span
+                stats = sums[:H, 1:3].reshape(-1).contiguous()
+                _allreduce_(stats)
+            # all H actors (k > 0), then all H critics (k < n_epochs)
+            opts = ([h.opt_actor for h in heads] if k > 0 else []) + ([h.opt_critic for h in heads] if crit else [])
+            nout = None
+            if norms is not None:
+                off = (k - 1) * 2 * H + H if k > 0 else 0
+                nout = norms.view(-1)[off:off + len(opts)]
+            _reduce_and_step(trained, opts, bucket, max_grad_norm, nout)
     if norms is not None:
         return [tuple(o) for o in out], norms
     return [tuple(o) for o in out]
-
-
-def _no_step_hooks(o):
-    """No optimizer step hooks (per instance or global): the fast path bypasses Optimizer.step."""
-    from torch.optim import optimizer as _opt
-    return not (getattr(o, "_optimizer_step_pre_hooks", None) or getattr(o, "_optimizer_step_post_hooks", None)
-                or getattr(_opt, "_global_optimizer_pre_hooks", None)
-                or getattr(_opt, "_global_optimizer_post_hooks", None))
-
-
-def _fused_adam_ok(o):
-    return (hasattr(torch, "_fused_adam_") and hasattr(torch, "_foreach_add_") and _no_step_hooks(o)
-            and isinstance(o, torch.optim.Adam) and getattr(o, "grad_scale", None) is None
-            and getattr(o, "found_inf", None) is None
-            and all(g.get("fused") and not g.get("amsgrad") and not g.get("capturable") and not g.get("differentiable")
-                    and not g.get("decoupled_weight_decay", False) and not isinstance(g["lr"], torch.Tensor)
-                    for g in o.param_groups))
-
-
-class _AdamPlan:
-    """The grouped tensor lists of one adam_steps(opts) call, reused while every optimiser keeps
-    the same state / param_groups objects, hyper-parameters and .grad tensors (an optimiser's
-    load_state_dict replaces those objects; a rebound .grad is a different tensor)."""
-
-    def __init__(self, opts, keys, groups, steps, grads):
-        self.opts, self.keys, self.groups, self.steps = opts, keys, groups, steps
-        # strong references, compared by identity: an id() of a state dict freed by a later
-        # load_state_dict could be reused by a newer one and pass a stale plan
-        self.refs = [(o.state, o.param_groups) for o in opts]
-        self.grads = grads  # [(param, grad)]
-
-    def valid(self, opts):
-        if len(opts) != len(self.refs) or not all(o.state is st and o.param_groups is pg
-                                                  for o, (st, pg) in zip(opts, self.refs)):
-            return False
-        if _group_keys(opts) != self.keys or not all(_no_step_hooks(o) for o in opts):
-            return False
-        return all(p.grad is g for p, g in self.grads)
-
-
-def _group_keys(opts):
-    return [(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["weight_decay"]), float(g["eps"]),
-             bool(g["maximize"])) for o in opts for g in o.param_groups]
-
-
-_ADAM_PLANS = {}
-
-
-def adam_steps(opts, max_grad_norm=None, norms_out=None):
-    """One step of every optimiser in `opts`.  max_grad_norm set (opt-in): every net's gradient is
-    clipped to that norm first and the step runs on the native clip-and-Adam launch
-    (adam_clip_steps below; norms_out as there); the rest of this text is the default, None.
-
-    Bit-identical to calling o.step() on each.  For
-    fused torch Adams (the GPU path) whose state exists, the steps of all six nets run as ONE
-    step-count increment and one torch._fused_adam_ launch per distinct hyper-parameter set —
-    the same per-tensor kernel arithmetic as each optimiser's own step (torch.optim.adam
-    _fused_adam), in 1 + (distinct lr) launches instead of 2 per optimiser.  Anything else (CPU,
-    the first step, which creates the state, non-default options, registered optimizer step
-    hooks, a torch without the private torch._fused_adam_ op) takes o.step().  The fast path
-    reads each group's lr at every call, so an LR scheduler's changes apply; it does not run
-    Optimizer.step itself (no step hooks — hence the fallback above — and no scheduler
-    step-order bookkeeping).  The grouped tensor lists are built once per optimiser set and
-    reused (_AdamPlan: ~0.2 ms of host time per call otherwise).  Pinned by
-    test_adam_steps_bit_identical_to_per_optimizer_steps."""
-    if max_grad_norm is not None:
-        return adam_clip_steps(opts, max_grad_norm, norms_out)
-    key = tuple(id(o) for o in opts)
-    plan = _ADAM_PLANS.get(key)
-    if plan is not None and plan.opts == list(opts) and plan.valid(opts):
-        _run_adam_plan(plan)
-        return
-    fast = all(_fused_adam_ok(o) for o in opts)
-    groups, steps, grads = {}, [], []
-    if fast:
-        for o in opts:
-            for g in o.param_groups:
-                ps = [p for p in g["params"] if p.grad is not None]
-                if any(len(o.state[p]) == 0 for p in ps):
-                    fast = False
-                    break
-                if not ps:
-                    continue
-                hk = (ps[0].device, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                      float(g["weight_decay"]), float(g["eps"]), bool(g["maximize"]))
-                e = groups.setdefault(hk, ([], [], [], [], []))
-                for p in ps:
-                    st = o.state[p]
-                    if p.dtype != torch.float32 or p.device != hk[0]:
-                        fast = False
-                    e[0].append(p)
-                    e[1].append(p.grad)
-                    e[2].append(st["exp_avg"])
-                    e[3].append(st["exp_avg_sq"])
-                    e[4].append(st["step"])
-                    steps.append(st["step"])
-                    grads.append((p, p.grad))
-            if not fast:
-                break
-    if not fast:
-        _ADAM_PLANS.pop(key, None)
-        for o in opts:
-            o.step()
-        return
-    plan = _AdamPlan(list(opts), _group_keys(opts), groups, steps, grads)
-    if len(_ADAM_PLANS) > 64:
-        _ADAM_PLANS.clear()
-    _ADAM_PLANS[key] = plan
-    _run_adam_plan(plan)
-
-
-def _run_adam_plan(plan):
-    torch._foreach_add_(plan.steps, 1)
-    for (_, lr, b1, b2, wd, eps, maximize), (ps, gs, ms, vs, sts) in plan.groups.items():
-        torch._fused_adam_(ps, gs, ms, vs, [], sts, amsgrad=False, lr=lr, beta1=b1, beta2=b2, weight_decay=wd,
-                           eps=eps, maximize=maximize, grad_scale=None, found_inf=None)
-
-
-# ------------------------------------------------- gradient-norm clipping + Adam (opt-in)
-# mhppo_adam_clip (include/mhppo.h, csrc/adam_clip.hip): per net the gradient norm in the fixed
-# fold order, the clip scale and the Adam step on the torch optimiser's own state, all nets of a
-# pipeline step in one launch.  adam_clip_torch is the contract's executable specification (the
-# tests compare the kernel with it bit for bit) and the CPU path.
-
-def fold_1024_4(x):
-    """The fold of a float64 vector in k_fold<1024, 4>'s order (csrc/block_prims.h): thread b's
-    chain u adds elements b + 1024 u (+ 4096 k) from +0.0, (a0 + a1) + (a2 + a3), the halving tree."""
-    x = x.reshape(-1)
-    n = x.numel()
-    rounds = max(1, -(-n // 4096))
-    pad = x.new_zeros(rounds * 4096)  # an absent element adds +0.0 to a chain that is never -0.0
-    pad[:n] = x
-    pad = pad.view(rounds, 4, 1024)
-    acc = x.new_zeros(4, 1024)
-    for r in range(rounds):
-        acc = acc + pad[r]
-    v = (acc[0] + acc[1]) + (acc[2] + acc[3])
-    s = 512
-    while s:
-        v = v[:s] + v[s:2 * s]
-        s //= 2
-    return v[0]
-
-
-def adam_clip_sumsq(grads):
-    """ss of the contract: the squares of the net's flat gradient (the tensors of `grads` in
-    order), exact in float64, folded in k_fold<1024, 4>'s order.  A float64 scalar tensor."""
-    g = torch.cat([x.detach().reshape(-1) for x in grads]).double()
-    return fold_1024_4(g * g)
-
-
-def _f32(x):
-    return torch.tensor(float(x), dtype=torch.float64).to(torch.float32)
-
-
-def adam_clip_torch(segs, t, lr, beta1, beta2, eps, max_norm, norm=None):
-    """mhppo_adam_clip's arithmetic for one net, operation for operation (include/mhppo.h), in
-    place on torch tensors: segs = [(param, grad, exp_avg, exp_avg_sq, step)] in flat order, t the
-    step count after the increment.  Returns the float64 norm before clipping (a Python float).
-    norm: use this value instead of sqrt(ss) (the tests feed the kernel's reported norm, so that a
-    last-bit difference of the float64 square root cannot move the comparison of the step)."""
-    if norm is None:
-        norm = math.sqrt(float(adam_clip_sumsq([s[1] for s in segs])))
-    coef = float(max_norm) / (norm + 1e-6)
-    s = _f32(coef) if coef < 1.0 else _f32(1.0)
-    a, q = _f32(lr / (1.0 - beta1 ** t)), _f32(math.sqrt(1.0 - beta2 ** t))
-    c1, b2, c2, e = _f32(1.0 - beta1), _f32(beta2), _f32(1.0 - beta2), _f32(eps)
-    with torch.no_grad():
-        for p, g, m, v, step in segs:
-            p, g = p.detach(), g.detach()
-            dev = p.device
-            gs = g * s.to(dev)
-            m.add_((gs - m) * c1.to(dev))
-            v.mul_(b2.to(dev)).add_((gs * gs) * c2.to(dev))
-            # sqrtf, correctly rounded: through float64 (a float32 root is never near enough to a
-            # rounding boundary for the second rounding to matter); torch's float32 CPU sqrt is a
-            # vectorised approximation that misses the IEEE result in ~0.6 % of the elements
-            den = (v.double().sqrt().float() / q.to(dev)) + e.to(dev)
-            p.sub_((m / den) * a.to(dev))
-            step.fill_(float(t))
-    return norm
-
-
-def _clip_group_ok(g):
-    return (not g.get("amsgrad") and not g.get("maximize") and not g.get("capturable")
-            and not g.get("differentiable") and not isinstance(g["lr"], torch.Tensor)
-            and float(g["weight_decay"]) == 0.0)
-
-
-class _ClipNet:
-    """One torch.optim.Adam as one net of a mhppo_adam_clip call: its parameters in order as the
-    segments, the state tensors' addresses and the host-side step count t.  t is read from the
-    state ONCE, when the record is built, and incremented per step; the record is rebuilt (and t
-    read again) when the optimiser's `state` or `param_groups` object, a state dict, a parameter's
-    storage or a `.grad` tensor is replaced (load_state_dict, .to(), zero_grad(set_to_none=True))
-    or a step hook appears.  What it cannot see is a step taken behind its back on the same state
-    objects (o.step(), adam_steps without max_grad_norm): clip_forget(opts) drops the records then.
-    ok is False for an optimiser the kernel does not serve (see adam_clip_steps)."""
-
-    def __init__(self, o):
-        self.opt, self.state, self.pg = o, o.state, o.param_groups
-        self.ok = False
-        if not (isinstance(o, torch.optim.Adam) and _no_step_hooks(o) and len(o.param_groups) == 1
-                and getattr(o, "grad_scale", None) is None and getattr(o, "found_inf", None) is None
-                and _clip_group_ok(o.param_groups[0])):
-            return
-        g = o.param_groups[0]
-        ps = [p for p in g["params"] if p.grad is not None]
-        if not ps or len(ps) > _lib.ADAM_MAX_SEGS:
-            return
-        dev = ps[0].device
-        if dev.type not in ("cuda", "cpu") or (dev.type == "cuda" and not g.get("fused")):
-            return  # a foreach / single-tensor GPU optimiser keeps `step` on the host
-        for p in ps:
-            if (p.dtype != torch.float32 or p.device != dev or not p.is_contiguous() or p.grad.dtype != torch.float32
-                    or p.grad.device != dev or not p.grad.is_contiguous()):
-                return
-        fresh = [p for p in ps if len(o.state[p]) == 0]
-        for p in fresh:  # the state torch's Adam._init_group would create at the first step
-            st = o.state[p]
-            st["step"] = (torch.zeros((), dtype=torch.float32, device=dev) if g.get("fused")
-                          else torch.tensor(0.0, dtype=torch.float32))
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        sts = [o.state[p] for p in ps]
-        for p, st in zip(ps, sts):
-            m, v, step = st.get("exp_avg"), st.get("exp_avg_sq"), st.get("step")
-            if not (torch.is_tensor(m) and torch.is_tensor(v) and torch.is_tensor(step)) or step.numel() != 1:
-                return
-            if step.dtype != torch.float32 or (dev.type == "cuda" and step.device != dev):
-                return
-            for x in (m, v):
-                if x.dtype != torch.float32 or x.device != dev or not x.is_contiguous() or x.numel() != p.numel():
-                    return
-        if len(fresh) == len(ps):
-            ts = {0}
-        else:  # one host read per optimiser and record
-            ts = {int(x) for x in torch.stack([st["step"].reshape(()).to(dev) for st in sts]).tolist()}
-        if len(ts) != 1:
-            return
-        self.t = ts.pop()
-        self.dev = dev
-        self.params = [(p, p.grad, p.data_ptr(), st) for p, st in zip(ps, sts)]
-        self.segs = [(p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["step"]) for p, st in zip(ps, sts)]
-        self.ok = True
-
-    def valid(self):
-        o = self.opt
-        if o.state is not self.state or o.param_groups is not self.pg or not _no_step_hooks(o):
-            return False
-        if not self.ok:
-            return False  # an unsupported optimiser is looked at again at every call
-        get = self.state.get
-        return _clip_group_ok(self.pg[0]) and all(p.grad is g and p.data_ptr() == ptr and get(p) is st
-                                                  for p, g, ptr, st in self.params)
-
-    def hyper(self):
-        """(t, lr, beta1, beta2, eps) of the step about to run: read at every call."""
-        g = self.pg[0]
-        return self.t + 1, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
-
-
-_CLIP_NETS = {}    # id(optimiser) -> _ClipNet
-_CLIP_PLANS = {}   # ids of an optimiser set -> (records, ctypes table)
-
-
-def clip_forget(opts=None):
-    """Drop the clip path's records of `opts` (default: all), so the next clipped step reads the
-    step counts from the optimisers' state again."""
-    for k in ([id(o) for o in opts] if opts is not None else list(_CLIP_NETS)):
-        _CLIP_NETS.pop(k, None)
-    _CLIP_PLANS.clear()
-
-
-def _clip_net(o):
-    rec = _CLIP_NETS.get(id(o))
-    if rec is None or rec.opt is not o or not rec.valid():
-        if len(_CLIP_NETS) > 256:
-            clip_forget()
-        rec = _CLIP_NETS[id(o)] = _ClipNet(o)
-    return rec
-
-
-def _clip_table(recs):
-    nets = (_lib.AdamNet * len(recs))()
-    for net, rec in zip(nets, recs):
-        net.n_seg = len(rec.segs)
-        for sg, (p, g, m, v, step) in zip(net.seg, rec.segs):
-            sg.param, sg.grad, sg.exp_avg, sg.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-            sg.step, sg.n = step.data_ptr(), p.numel()
-    return nets
-
-
-def _clip_launch(recs, nets, max_norm, norms):
-    """One mhppo_adam_clip call for `recs` (all on one GPU) on the current stream."""
-    hs = [rec.hyper() for rec in recs]
-    for net, (t, lr, b1, b2, eps) in zip(nets, hs):
-        net.t, net.alpha, net.bias2 = t, lr / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t)
-        net.beta1, net.beta2, net.eps = b1, b2, eps
-    dev = recs[0].dev
-    with (contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)):
-        _lib.adam_clip(nets, len(recs), max_norm, norms.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    for rec in recs:
-        rec.t += 1
-
-
-def adam_clip_steps(opts, max_grad_norm, norms_out=None):
-    """adam_steps with the knob set: per optimiser (= per net) clip the gradient to max_grad_norm
-    (> 0; inf clips nothing and only measures), then one Adam step.  Returns the float64 norms
-    before clipping, one per optimiser in order, in norms_out (float64, contiguous,
-    len(opts) elements, on the nets' device) or a new tensor; nothing is read back to the host.
-
-    GPU: ONE mhppo_adam_clip launch for all optimisers of the call (include/mhppo.h has the
-    arithmetic), on the optimisers' own state tensors: state_dict() and the checkpoints stay the
-    truth.  The first step is native too: where torch has not created the Adam state yet it is
-    created here as Adam._init_group would (zero moments, a float32 device scalar `step`).  The
-    segment table is built once per optimiser set and reused under _AdamPlan's rule (identity of
-    state / param_groups / .grad, plus the parameters' addresses; _ClipNet says what rebuilds it
-    and what the host-side step count cannot see); lr, betas and eps are read at every call, so a
-    scheduler's changes apply.  CPU tensors (the test doubles) take adam_clip_torch, the same
-    arithmetic: CPU and GPU runs of one seed agree bit for bit in the optimiser.
-    Fallback: an optimiser the kernel does not serve (not torch.optim.Adam, weight_decay, amsgrad,
-    maximize, capturable, differentiable, a tensor lr, several param groups, more than 8 parameter
-    tensors, non-float32 or non-contiguous tensors, a GPU optimiser that is not fused=True (its
-    `step` lives on the host), step hooks) takes torch.nn.utils.clip_grad_norm_ on its
-    parameters, then o.step(); the others of the call still go native, one launch each."""
-    max_norm = float(max_grad_norm)
-    if not max_norm > 0.0:
-        raise ValueError(f"max_grad_norm must be > 0 (inf allowed), not {max_grad_norm!r}")
-    opts = list(opts)
-    if not opts:
-        return norms_out
-    key = tuple(id(o) for o in opts)
-    plan = _CLIP_PLANS.get(key)
-    if plan is not None and all(_CLIP_NETS.get(k) is rec and rec.valid() for k, rec in zip(key, plan[0])):
-        recs, nets = plan
-    else:
-        recs, nets = [_clip_net(o) for o in opts], None
-        _CLIP_PLANS.pop(key, None)
-    dev = recs[0].dev if recs[0].ok else next((p.device for p in opts[0].param_groups[0]["params"]), None)
-    if norms_out is None:
-        norms_out = torch.empty(len(opts), dtype=torch.float64, device=dev)
-    elif norms_out.dtype != torch.float64 or not norms_out.is_contiguous() or norms_out.numel() != len(opts):
-        raise ValueError("norms_out must be a contiguous float64 tensor with one element per optimiser")
-    if all(r.ok and r.dev.type == "cuda" and r.dev == dev for r in recs) and norms_out.device == dev:
-        if nets is None:
-            nets = _clip_table(recs)
-            if len(_CLIP_PLANS) > 64:
-                _CLIP_PLANS.clear()
-            _CLIP_PLANS[key] = (recs, nets)
-        _clip_launch(recs, nets, max_norm, norms_out)
-        return norms_out
-    for k, (o, rec) in enumerate(zip(opts, recs)):
-        if rec.ok and rec.dev.type == "cuda":
-            one = norms_out[k:k + 1] if norms_out.device == rec.dev else torch.empty(1, dtype=torch.float64,
-                                                                                     device=rec.dev)
-            _clip_launch([rec], _clip_table([rec]), max_norm, one)
-            if one.device != norms_out.device:
-                norms_out[k:k + 1].copy_(one)
-        elif rec.ok:
-            t, lr, b1, b2, eps = rec.hyper()
-            norms_out[k] = adam_clip_torch(rec.segs, t, lr, b1, b2, eps, max_norm)
-            rec.t += 1
-        else:
-            ps = [p for g in o.param_groups for p in g["params"] if p.grad is not None]
-            norms_out[k] = torch.nn.utils.clip_grad_norm_(ps, max_norm).detach().double()
-            o.step()
-    return norms_out
 
 
 def train_model_c(actor, critic, opt_actor, opt_critic, obs, act, logp_old, ret, m_global, exact=False):

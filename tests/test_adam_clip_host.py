@@ -155,14 +155,19 @@ def test_cpu_path_is_the_specification():
 
 
 def test_knob_off_takes_optimizer_step(monkeypatch):
-    from mhppo import ppo
+    from mhppo import adam, ppo
     nets, opts = _cpu_nets()
     calls = []
     for o in opts:
         monkeypatch.setattr(o, "step", lambda o=o: calls.append(id(o)))
-    monkeypatch.setattr(ppo, "adam_clip_steps", lambda *a, **k: pytest.fail("the clip path ran with the knob off"))
+    reached = []  # replaced in mhppo.adam, where adam_steps looks the name up
+    monkeypatch.setattr(adam, "adam_clip_steps", lambda *a, **k: reached.append(a))
+    assert ppo.adam_steps is adam.adam_steps
+    ppo.adam_steps(opts, max_grad_norm=0.5)  # the replacement is live: the knob reaches it
+    assert len(reached) == 1 and calls == []
     assert ppo.adam_steps(opts) is None
     assert calls == [id(o) for o in opts]
+    assert len(reached) == 1, "the clip path ran with the knob off"
 
 
 def test_unsupported_optimizer_takes_the_torch_fallback():
@@ -188,16 +193,16 @@ def test_every_gradient_allreduce_precedes_the_clip(monkeypatch):
     from test_dp_gloo import _install_cpu_doubles
     from mhppo import ppo
     from mhppo.models import Model_PPO
-    for name in ("k_adv_stats", "k_adv_normalize", "k_mse", "k_ppo_cont", "k_mlp_train", "k_mlp_train_pair",
-                 "_critic_pass", "_actor_pass", "_pair_pass"):
+    from mhppo import adam
+    for name in ("k_adv_stats", "k_adv_normalize", "k_mse", "k_ppo_cont", "_critic_pass", "_actor_pass", "_pair_pass"):
         monkeypatch.setattr(ppo, name, getattr(ppo, name))  # restored after the test
     _install_cpu_doubles(ppo)
     events = []
     monkeypatch.setattr(ppo, "_dp", lambda: True)  # one rank: a SUM all-reduce is the identity
     monkeypatch.setattr(ppo.dist, "all_reduce",
                         lambda t, op=None: events.append("grad" if t.dtype == torch.float32 else "stats"))
-    real = ppo.adam_clip_steps
-    monkeypatch.setattr(ppo, "adam_clip_steps", lambda *a, **k: (events.append("clip"), real(*a, **k))[1])
+    real = adam.adam_clip_steps  # replaced where adam_steps looks it up
+    monkeypatch.setattr(adam, "adam_clip_steps", lambda *a, **k: (events.append("clip"), real(*a, **k))[1])
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
     nets = [Model_PPO(13, 1, 1, mean=-1.0, std=3.0), Model_PPO(13, 1, 1, mean=-1.0, std=3.0), Model_PPO(13, 1, 0),

@@ -99,10 +99,9 @@ def _install_cpu_doubles(ppo):
         return actor.grad_flat(), critic.grad_flat(), value
 
     ppo.k_adv_stats, ppo.k_adv_normalize, ppo.k_mse, ppo.k_ppo_cont = adv_stats, adv_normalize, mse, ppo_cont
-    ppo.k_mlp_train = mlp_train
-    ppo.k_mlp_train_pair = mlp_train_pair
 
-    # train_epochs' launch helpers (ppo._HeadPlan arguments) on the same doubles
+    # train_epoch's / train_epochs' pass helpers (ppo._HeadPlan arguments), the only way the
+    # orchestration reaches the train kernels, on the doubles above
     def critic_pass(p, h, sums, st):
         p.V.copy_(mlp_train(0, h.critic, p.obs, p.ret, m_global=h.m, sums=sums)[2])
 

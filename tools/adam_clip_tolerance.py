@@ -1,4 +1,4 @@
-"""The accuracy of the clip-and-Adam contract (mhppo.ppo.adam_clip_torch = mhppo_adam_clip) and of
+"""The accuracy of the clip-and-Adam contract (mhppo.adam.adam_clip_torch = mhppo_adam_clip) and of
 today's float32 path, both against float64: clip_grad_norm_ + torch.optim.Adam on float64 CPU copies,
 three steps, six nets of the product's sizes, max_norm between the nets' norms
 (tests/adam_clip_common.py accuracy_case).  error = |d| / max(1, |ref|) over all parameters.
