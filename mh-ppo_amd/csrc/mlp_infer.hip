@@ -60,11 +60,11 @@ __global__ void __launch_bounds__(ITPB) k_mlp_forward(NetArg net, int kind, int 
         const int64_t r = r0 + j;
         if (NOUT == 2) {
           float p0, p1;
-          finish_choice(z[0], z[NOUT - 1], p0, p1);
+          softmax_pair<LibmRollout>(z[0], z[NOUT - 1], p0, p1);
           out[2 * r] = p0;
           out[2 * r + 1] = p1;
         } else {
-          out[r] = kind == 1 ? finish_cont(z[0], net.mean, net.std) : z[0];
+          out[r] = kind == 1 ? finish_cont<LibmRollout>(z[0], net.mean, net.std) : z[0];
         }
       }
     }

@@ -1,15 +1,13 @@
-// mlp_infer_terms.h — what follows a Model_PPO head's last layer outside the rollout, and the
-// per-row terms of the PPO diagnostics (host+device: mlp_infer.hip runs them on the GPU,
-// tools/hostfwd.cpp compiles this very source for the CPU reference).
+// mlp_infer_terms.h — the per-row terms of the PPO diagnostics (host+device: mlp_infer.hip runs
+// them on the GPU, tools/hostfwd.cpp compiles this very source for the CPU reference).
 //
-// The head finishes restate the rollout's, operation for operation: finish_cont is
-// k_policy_mfma's tanh * std + mean (two roundings, Model_PPO :87-89), finish_choice k_choice's
-// pairwise softmax (:81-85), choice_logp its Categorical log-prob (normalise, clamp to
-// [eps, 1 - eps], logf; torch/distributions/utils.py).  With the same weights and feature row they
+// The head finishes are the rollout's own functions (ppo_heads.h, the LibmRollout flavour):
+// finish_cont is the policy kernels' tanh * std + mean, softmax_pair k_choice's pairwise softmax,
+// cat_normalise / cat_clamp its Categorical log-prob.  With the same weights and feature row they
 // return the rollout's bits, so a diagnostic d = logp_new - logp_old is exactly 0 before an update.
 #pragma once
 #include "../../include/mhppo.h"
-#include "libm_glibc.h"
+#include "ppo_heads.h"
 #include "rollout_dev.h"
 
 namespace mhppo {
@@ -17,31 +15,7 @@ namespace infer {
 
 constexpr int N_IN_MAX = 64;  // widest input (the scalable 8-slot choice head: 54)
 
-MHPPO_HD inline float finish_cont(float z, float mean, float std) {
-  float t = mhppo_tanhf(z) * std;
-  return t + mean;
-}
-
-MHPPO_HD inline void finish_choice(float z0, float z1, float &p0, float &p1) {
-  float mx = z0 > z1 ? z0 : z1;
-  float ex0 = mhppo_expf(z0 - mx), ex1 = mhppo_expf(z1 - mx);
-  float s = ex0 + ex1;
-  p0 = ex0 / s;
-  p1 = ex1 / s;
-}
-
-// Categorical(probs).log_prob(a) as k_choice writes it; n0 / n1: the normalised, clamped pair
-MHPPO_HD inline float choice_logp(float p0, float p1, int a, float &n0, float &n1) {
-  const float eps = 1.1920928955078125e-07f, hi = 1.0f - 1.1920928955078125e-07f;
-  float sum = p0 + p1;
-  n0 = p0 / sum;
-  n1 = p1 / sum;
-  n0 = n0 < eps ? eps : (n0 > hi ? hi : n0);
-  n1 = n1 < eps ? eps : (n1 > hi ? hi : n1);
-  return logf(a ? n1 : n0);
-}
-
-// entropy of that pair in float64
+// entropy of the normalised, clamped pair in float64
 MHPPO_HD inline double choice_entropy(float n0, float n1) {
   const double a = (double)n0, b = (double)n1;
   return -(a * log(a) + b * log(b));
@@ -78,12 +52,15 @@ MHPPO_HD inline double diag_row(int kind, const float *za, float mean, float std
   float lp;
   double ent = 0.0;
   if (kind == 2) {
-    float p0, p1, n0, n1;
-    finish_choice(za[0], za[1], p0, p1);
-    lp = choice_logp(p0, p1, act_i, n0, n1);
-    ent = choice_entropy(n0, n1);
+    float p0, p1, n[2];
+    softmax_pair<LibmRollout>(za[0], za[1], p0, p1);
+    cat_normalise(p0, p1, n);
+    n[0] = cat_clamp(n[0]);
+    n[1] = cat_clamp(n[1]);
+    lp = logf(act_i ? n[1] : n[0]);  // Categorical(probs).log_prob(a) as k_choice writes it
+    ent = choice_entropy(n[0], n[1]);
   } else {
-    lp = mvn_logp(act_f, finish_cont(za[0], mean, std));
+    lp = mvn_logp(act_f, finish_cont<LibmRollout>(za[0], mean, std));
   }
   if (lp_new) *lp_new = lp;
   critic_terms(ret, vc, t);

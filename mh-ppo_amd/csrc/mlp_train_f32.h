@@ -29,6 +29,8 @@
 //             broadcast (:828-842) in its exact O(M) form: each row contributes
 //             sum_k counts[k] * f(r_k, A) with r_k = p_k / exp(logp_old); dL/dp through the
 //             pn = p / sum(p) normalisation and the clamp, then the softmax Jacobian.
+// The per-row arithmetic of the three kinds is ppo_heads.h's (one copy, with host tests); the few
+// places where a call would change a train kernel's instruction text restate it and say so.
 // The 13-input heads (PF: critic / continuous actor) run 8 waves per block (2 per SIMD, <= 256
 // VGPRs) with the next tile's inputs prefetched into a double-buffered LDS slot by LDS-DMA; the
 // other instantiations (choice obs of up to 64 features) run 4 waves and load the next tile
@@ -40,7 +42,8 @@
 #include <math.h>
 
 #include "mlp_tile.h"
-#include "rollout_dev.h"  // surr_and_grad, the MVN constants (ppo_math.h), MHPPO_MARK
+#include "ppo_heads.h"    // the heads' per-row arithmetic; surr_and_grad (ppo_math.h)
+#include "rollout_dev.h"  // MHPPO_MARK
 
 using namespace mhppo;
 
@@ -173,7 +176,7 @@ __global__ void __launch_bounds__(PF ? 512 : 256)  // 64 * Lay::WAVES
   double *dacc = reinterpret_cast<double *>(lds + LY::O_DACC) + w * 96 + j;
   if (kh == 0) dacc[0] = dacc[32] = dacc[64] = 0.0;
   float meanf = 0.f, stdf = 1.f;
-  if (KIND != K_CRITIC) {
+  if (KIND != K_CRITIC) {  // ppo_heads.h adv_moments, restated (stats[1] is loaded after the mean's division)
     double mean = stats[0] / m_global;
     double var = (stats[1] - stats[0] * mean) / (m_global - 1.0);
     meanf = (float)mean;
@@ -278,31 +281,29 @@ __global__ void __launch_bounds__(PF ? 512 : 256)  // 64 * Lay::WAVES
         }
         dy0 = (float)(2.0 * inv_m * (double)d);
       } else if constexpr (KIND == K_CONT) {
-        const float t = tanhf(y0);
-        const float mu = t * out_std + out_mean;
-        const float a = rt - slot[LY::IN_S0 + 32 + j];
-        const float A = (a - meanf) / (stdf + 1e-10f);
-        const float diff = (float)((double)slot[LY::IN_S1 + j] - (double)mu);
-        const float x = diff * MVN_INV_L;
-        const float lp = (-0.5f * (MVN_LOG2PI + x * x)) - MVN_HALF_LOGDET;
+        float t, x;
+        const float mu = finish_cont<LibmUpdate>(y0, out_mean, out_std, t);
+        const float A = adv_normalised(rt - slot[LY::IN_S0 + 32 + j], meanf, stdf);
+        const float lp = cont_logp_x(slot[LY::IN_S1 + j], mu, x);
         const double r = exp((double)lp - (double)slot[LY::IN_S1 + 32 + j]);
         double dfdr;
         const double f = surr_and_grad(r, (double)A, dfdr);
         if (kh == 0) dacc[0] += f;
-        const float dmu = (float)(inv_m * dfdr * r * (double)x * (double)MVN_INV_L);
+        const float dmu = cont_dmu(inv_m, dfdr, r, x);
         dy0 = (dmu * out_std) * (1.0f - t * t);
       } else {
+        // This branch restates ppo_heads.h softmax_pair, cat_normalise, choice_term, cat_grad_p and
+        // softmax_jacobian (calls compile to other code in the n_in > 32 instantiations).
         // softmax over the pair (as torch: shift by the max), pn = p / (p0 + p1)
         const float mx = fmaxf(y0, y1);
         const float e0 = expf(y0 - mx), e1 = expf(y1 - mx);
         const float se = e0 + e1;
         const float p[2] = {e0 / se, e1 / se};
-        const float a = rt - slot[LY::IN_S0 + 32 + j];
-        const float A = (a - meanf) / (stdf + 1e-10f);
+        const float A = adv_normalised(rt - slot[LY::IN_S0 + 32 + j], meanf, stdf);
         const double old = (double)slot[LY::IN_S1 + j];
         const float sp = p[0] + p[1];
         const float pn[2] = {p[0] / sp, p[1] / sp};
-        const float eps = 1.1920928955078125e-07f, hi = 1.0f - 1.1920928955078125e-07f;
+        const float eps = CAT_EPS, hi = CAT_HI;
         const double inv_m2 = inv_m * inv_m;
         // reference: every row meets every action with the global counts (the M x M
         // broadcast); per-row mode (counts == NULL, opt-in bug fix): the row's own action
@@ -316,7 +317,7 @@ __global__ void __launch_bounds__(PF ? 512 : 256)  // 64 * Lay::WAVES
           const double r = exp((double)logf(pc) - old);
           double dfdr;
           const double fk = surr_and_grad(r, (double)A, dfdr);
-          if (w != 0.0) f += w * fk;
+          if (w != 0.0) f += w * fk;  // weight 0 (per-row: the other action) is no term: 0 * inf stays out
           const double pass = (pn[k] >= eps && pn[k] <= hi) ? 1.0 : 0.0;
           dlp[k] = inv_m2 * w * dfdr * r * pass / (double)pc;  // dL/dpn_k
         }

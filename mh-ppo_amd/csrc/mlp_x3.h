@@ -38,7 +38,8 @@
 
 #include "mlp_tile.h"
 #include "mlp_x3_prims.h"
-#include "rollout_dev.h"  // surr_and_grad, surr_and_grad_fd, the MVN constants (ppo_math.h), MHPPO_MARK
+#include "ppo_heads.h"    // the heads' per-row arithmetic; surr_and_grad, surr_and_grad_fd (ppo_math.h)
+#include "rollout_dev.h"  // MHPPO_MARK
 
 using namespace mhppo;
 
@@ -403,13 +404,10 @@ struct Pass {
         }
         dy0 = (float)(2.0 * inv_m * (double)d);
       } else if constexpr (KIND == K_CONT) {
-        const float t = tanhf(y0);
-        const float mu = t * out_std + out_mean;
-        const float a = rt - slot[G::IN_S0 + 32 + j];
-        const float A = (a - meanf) / (stdf + 1e-10f);
-        const float diff = (float)((double)slot[G::IN_S1 + j] - (double)mu);
-        const float x = diff * MVN_INV_L;
-        const float lp = (-0.5f * (MVN_LOG2PI + x * x)) - MVN_HALF_LOGDET;
+        float t, x;
+        const float mu = finish_cont<LibmUpdate>(y0, out_mean, out_std, t);
+        const float A = adv_normalised(rt - slot[G::IN_S0 + 32 + j], meanf, stdf);
+        const float lp = cont_logp_x(slot[G::IN_S1 + j], mu, x);
         // the ratio's magnitude in float32, its clip branch decided in float64 (see the note at
         // the head of this file)
         const float lpo = slot[G::IN_S1 + 32 + j];
@@ -417,43 +415,37 @@ struct Pass {
         float dfdr;
         const float f = surr_and_grad_fd(r, (double)lp - (double)lpo, A, dfdr);
         if (kh == 0) dsum0 += (double)f;
-        const float dmu = (float)(inv_m * (double)dfdr * (double)r * (double)x * (double)MVN_INV_L);
+        const float dmu = cont_dmu(inv_m, dfdr, r, x);
         dy0 = (dmu * out_std) * (1.0f - t * t);
       } else {
-        // choice actor (train_model_d :818-851): softmax over the pair (as torch: shift by the
-        // max), pn = p / (p0 + p1), the M x M Categorical broadcast in its O(M) form with the
-        // global action counts (or the opt-in per-row loss: the row's own action, weight M)
-        const float mx = fmaxf(y0, y1);
-        const float e0 = expf(y0 - mx), e1 = expf(y1 - mx);
-        const float se = e0 + e1;
-        const float p[2] = {e0 / se, e1 / se};
-        const float a = rt - slot[G::IN_S0 + 32 + j];
-        const float A = (a - meanf) / (stdf + 1e-10f);
+        // choice actor (train_model_d :818-851): the M x M Categorical broadcast in its O(M) form
+        // with the global action counts (or the opt-in per-row loss: the row's own action, weight M)
+        float p[2], pn[2];
+        softmax_pair<LibmUpdate>(y0, y1, p[0], p[1]);
+        const float A = adv_normalised(rt - slot[G::IN_S0 + 32 + j], meanf, stdf);
         const double old = (double)slot[G::IN_S1 + j];
-        const float sp = p[0] + p[1];
-        const float pn[2] = {p[0] / sp, p[1] / sp};
-        const float eps = 1.1920928955078125e-07f, hi = 1.0f - 1.1920928955078125e-07f;
+        const float sp = cat_normalise(p[0], p[1], pn);
         const double inv_m2 = inv_m * inv_m;
         const int a_row = counts ? 0 : (int)slot[G::IN_S1 + 32 + j];
         double dlp[2], f = 0.0;
 #pragma unroll
-        for (int k = 0; k < 2; k++) {
+        for (int k = 0; k < 2; k++) {  // the body restates ppo_heads.h choice_term (a call compiles to other code)
           const double wk = counts ? counts[k] : (k == a_row ? m_global : 0.0);
-          const float pc = pn[k] < eps ? eps : (pn[k] > hi ? hi : pn[k]);
+          const float pc = pn[k] < CAT_EPS ? CAT_EPS : (pn[k] > CAT_HI ? CAT_HI : pn[k]);
           const double r = exp((double)logf(pc) - old);
           double dfdr;
           const double fk = surr_and_grad(r, (double)A, dfdr);
-          if (wk != 0.0) f += wk * fk;
-          const double pass = (pn[k] >= eps && pn[k] <= hi) ? 1.0 : 0.0;
+          if (wk != 0.0) f += wk * fk;  // weight 0 (per-row: the other action) is no term: 0 * inf stays out
+          const double pass = (pn[k] >= CAT_EPS && pn[k] <= CAT_HI) ? 1.0 : 0.0;
           dlp[k] = inv_m2 * wk * dfdr * r * pass / (double)pc;  // dL/dpn_k
         }
         if (kh == 0) dsum0 += f;
-        const double sd = (double)sp;
-        const double g0 = (dlp[0] * (1.0 - pn[0]) - dlp[1] * pn[1]) / sd;  // dL/dp_k
-        const double g1 = (dlp[1] * (1.0 - pn[1]) - dlp[0] * pn[0]) / sd;
-        const double dot = (double)p[0] * g0 + (double)p[1] * g1;
-        dy0 = (float)((double)p[0] * (g0 - dot));  // softmax Jacobian
-        dy1 = (float)((double)p[1] * (g1 - dot));
+        double g0, g1;
+        cat_grad_p(dlp, pn, sp, g0, g1);
+        float d0, d1;  // not dy0 / dy1 themselves: as out-arguments they would stay in memory until the call is inlined
+        softmax_jacobian(p, g0, g1, d0, d1);
+        dy0 = d0;
+        dy1 = d1;
       }
     }
     radd(1, (kh == 0) ? dy0 : 0.0f);
@@ -1073,7 +1065,8 @@ struct Pass {
   }
 };
 
-// the normalisation of the actor's advantage from the critic pass's global sums
+// the normalisation of the actor's advantage from the critic pass's global sums: ppo_heads.h
+// adv_moments, restated (each moment is made wave-uniform as it is rounded)
 __device__ __forceinline__ void adv_norm(const double *stats, double m_global, float &meanf, float &stdf) {
   double mean = stats[0] / m_global;
   double var = (stats[1] - stats[0] * mean) / (m_global - 1.0);

@@ -12,7 +12,7 @@
 #include "block_prims.h"
 #include "common.h"
 #include "launch1d.h"
-#include "ppo_math.h"  // surr_and_grad, the MVN constants
+#include "ppo_heads.h"  // the heads' per-row arithmetic; surr_and_grad (ppo_math.h)
 
 using namespace mhppo;
 
@@ -46,11 +46,9 @@ __global__ void __launch_bounds__(TPB)
     k_adv_norm(const float *ret, const float *val, int64_t M, const double *stats, double mg, float *adv) {
   int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= M) return;
-  double mean = stats[0] / mg;
-  double var = (stats[1] - stats[0] * mean) / (mg - 1.0);
-  float meanf = (float)mean, stdf = (float)sqrt(var > 0 ? var : 0.0);
-  float a = ret[i] - val[i];
-  adv[i] = (a - meanf) / (stdf + 1e-10f);
+  float meanf, stdf;
+  adv_moments(stats, mg, meanf, stdf);
+  adv[i] = adv_normalised(ret[i] - val[i], meanf, stdf);
 }
 
 __global__ void __launch_bounds__(TPB)
@@ -59,16 +57,13 @@ __global__ void __launch_bounds__(TPB)
   int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
   double v[1] = {0.0};
   if (i < M) {
-    // log_prob(action f64) (:800): diff in float64 then float32 solve, float32 tail
-    float diff = (float)((double)act[i] - (double)mu[i]);
-    float x = diff * MVN_INV_L;
-    float lp = (-0.5f * (MVN_LOG2PI + x * x)) - MVN_HALF_LOGDET;
+    float x;
+    float lp = cont_logp_x(act[i], mu[i], x);  // log_prob(action f64) (:800)
     double r = exp((double)lp - (double)lp_old[i]);  // float64 ratio (:803)
     double dfdr;
     double f = surr_and_grad(r, (double)adv[i], dfdr);
     v[0] = f;
-    // dlogp/dmu = x / L  (d/dmu of -0.5 ((a - mu)/L)^2)
-    dmu[i] = (float)(inv_m * dfdr * r * (double)x * (double)MVN_INV_L);
+    dmu[i] = cont_dmu(inv_m, dfdr, r, x);
   }
   block_reduce_store<1>(v, partials, gridDim.x);
 }
@@ -80,28 +75,19 @@ __global__ void __launch_bounds__(TPB)
   int64_t j = (int64_t)blockIdx.x * TPB + threadIdx.x;
   double v[1] = {0.0};
   if (j < M) {
-    const float eps = 1.1920928955078125e-07f, hi = 1.0f - 1.1920928955078125e-07f;
-    float p0 = probs[2 * j], p1 = probs[2 * j + 1];
-    float s = p0 + p1;
-    float pn[2] = {p0 / s, p1 / s};
+    float pn[2];
+    const float s = cat_normalise(probs[2 * j], probs[2 * j + 1], pn);
     double A = adv[j], old = lp_old[j];
     double dlp[2];
     double f = 0.0;
     for (int k = 0; k < 2; k++) {
-      float pc = pn[k] < eps ? eps : (pn[k] > hi ? hi : pn[k]);
-      float lp = logf(pc);
-      double r = exp((double)lp - old);
-      double dfdr;
-      double fk = surr_and_grad(r, A, dfdr);
-      f += counts[k] * fk;
-      double pass = (pn[k] >= eps && pn[k] <= hi) ? 1.0 : 0.0;
-      dlp[k] = inv_m2 * counts[k] * dfdr * r * pass / (double)pc;  // dL/dpn_k
+      double fk;
+      dlp[k] = choice_term(pn[k], old, A, counts[k], inv_m2, fk);
+      f += counts[k] * fk;  // every term, as the count-weighted sum is written (the train kernels skip weight 0)
     }
     v[0] = f;
-    // pn_k = p_k / (p0 + p1)
-    double sd = (double)s;
-    double g0 = (dlp[0] * (1.0 - pn[0]) - dlp[1] * pn[1]) / sd;
-    double g1 = (dlp[1] * (1.0 - pn[1]) - dlp[0] * pn[0]) / sd;
+    double g0, g1;
+    cat_grad_p(dlp, pn, s, g0, g1);
     dprobs[2 * j] = (float)g0;
     dprobs[2 * j + 1] = (float)g1;
   }

@@ -1,7 +1,9 @@
 // ppo_math.h — the scalar arithmetic the rollout, the losses and the train kernels share, free of
 // the env (host+device): the MVN(loc, diag(0.5)) sample / log-prob constants, the clipped PPO
-// surrogate with its gradient, torch.minimum, and Philox-4x32-10.  rollout_dev.h includes it; the
-// units that need nothing of the env (noise.hip, ppo_batch.hip, ppo_loss.hip) include it alone.
+// surrogate with its gradient, torch.minimum, and Philox-4x32-10.  ppo_heads.h builds the heads'
+// per-row arithmetic (finishes, Categorical, advantage, loss rows) on it.  rollout_dev.h includes
+// it; the units that need nothing of the env include it alone (noise.hip, ppo_batch.hip) or through
+// ppo_heads.h (ppo_loss.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

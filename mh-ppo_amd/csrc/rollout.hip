@@ -29,7 +29,7 @@
 #include "common.h"
 #include "env_body.h"
 #include "launch1d.h"
-#include "libm_glibc.h"
+#include "ppo_heads.h"
 #include "rollout_dev.h"
 #include "rollout_policy.h"
 #include "rollout_lists.h"
@@ -92,22 +92,15 @@ __global__ void __launch_bounds__(TPB)
     if (dc == 54) mlp_forward_rows<54, 2>(W, f, pr);
     else if (dc == 27) mlp_forward_rows<27, 2>(W, f, pr);
     else mlp_forward<0, 2>(W, dc, f, pr);
-    // Softmax over the pair (Model_PPO type 2, :81-85)
-    float mx = pr[0] > pr[1] ? pr[0] : pr[1];
-    float ex0 = mhppo_expf(pr[0] - mx), ex1 = mhppo_expf(pr[1] - mx);
-    float s = ex0 + ex1;
-    float p0 = ex0 / s, p1 = ex1 / s;
+    float p0, p1, n[2];
+    softmax_pair<LibmRollout>(pr[0], pr[1], p0, p1);  // Model_PPO type 2 (:81-85)
     reinterpret_cast<float2 *>(B.probs_d)[r] = make_float2(p0, p1);
     if ((p0 != p0 || p1 != p1) && B.status) atomicOr(B.status, 1u);  // Categorical raises on NaN probs
     // Categorical(probs): normalise, clamp to [eps, 1-eps], log (torch/distributions/utils.py)
-    float sum = p0 + p1;
-    float n0 = p0 / sum, n1 = p1 / sum;
-    int a = forced ? forced[r] : (u[r] >= n0 ? 1 : 0);
-    const float eps = 1.1920928955078125e-07f, hi = 1.0f - 1.1920928955078125e-07f;
-    float pn = a ? n1 : n0;
-    pn = pn < eps ? eps : (pn > hi ? hi : pn);
+    cat_normalise(p0, p1, n);
+    int a = forced ? forced[r] : (u[r] >= n[0] ? 1 : 0);
     B.a_d[r] = a;
-    B.logp_d[r] = logf(pn);
+    B.logp_d[r] = logf(cat_clamp(a ? n[1] : n[0]));
   }
   __syncthreads();
   // the block's feature rows [r0, r0 + nr) x dc: one contiguous run of floats

@@ -9,7 +9,7 @@
 // Part of the rollout.hip translation unit (one anonymous namespace); not for inclusion elsewhere.
 #pragma once
 #include "launch1d.h"
-#include "libm_glibc.h"
+#include "ppo_heads.h"
 #include "mfma_tile.h"
 #include "rollout_dev.h"
 
@@ -70,9 +70,7 @@ __global__ void __launch_bounds__(TPB) k_policy(Cfg c, mhppo_mlp mc, mhppo_mlp m
   const mhppo_mlp &m = wait ? mw : mc;
   float out;
   mlp_forward<NF_C, 1>(W, NF_C, f, &out);
-  // Model_PPO type 1: tanh(x) * std + mean (:87-89), two roundings
-  float t = mhppo_tanhf(out) * m.std;
-  B.out_c[r] = t + m.mean;
+  B.out_c[r] = finish_cont<LibmRollout>(out, m.mean, m.std);  // Model_PPO type 1 (:87-89)
 }
 
 // Head-sorted policy step.  mhppo_rollout_begin lists the rows (env, slot, ped) of the
@@ -118,9 +116,7 @@ __global__ void __launch_bounds__(TPB) k_policy_sorted(Cfg c, const float *__res
   }
   if (L.scalable && ex == 0.0f) return;  // `if exist:` gate of the scalable driver (:439)
   const float out = mlp_forward13_rows(head ? Ww : Wc, f);
-  // Model_PPO type 1: tanh(x) * std + mean (:87-89), two roundings
-  const float t = mhppo_tanhf(out) * (head ? std_w : std_c);
-  B.out_c[r] = t + (head ? mean_w : mean_c);
+  B.out_c[r] = finish_cont<LibmRollout>(out, head ? mean_w : mean_c, head ? std_w : std_c);  // type 1 (:87-89)
 }
 #endif  // MHPPO_TEST_KERNELS
 
@@ -336,6 +332,7 @@ k_policy_mfma(Cfg c, const float *__restrict__ Wc,
     }
     const float out = actor_tile(Wl, f, j, kh);
     if (valid && kh == 0 && !(L.scalable && ex == 0.0f)) {  // `if exist:` gate (:439)
+      // ppo_heads.h finish_cont<LibmRollout>, restated (the mean is picked after the product: a call picks it before)
       const float t = mhppo_tanhf(out) * (head ? std_w : std_c);  // Model_PPO type 1 (:87-89)
       B.out_c[r] = t + (head ? mean_w : mean_c);
     }

@@ -10,7 +10,7 @@
 #pragma once
 #include "env_body.h"
 #include "launch1d.h"
-#include "libm_glibc.h"
+#include "ppo_heads.h"
 #include "rollout_dev.h"
 #include "rollout_policy.h"
 
@@ -263,10 +263,9 @@ __global__ void __launch_bounds__(TPB) k_eval_step(Cfg c, Bufs eb, mhppo_mlp mc,
         float fd[2 + 6 * (MAXS - 1) + 10], pr[2];
         obs_car_ped_d(o, L, i, p, fd);
         mlp_forward<0, 2>(Wd, dc, fd, pr);
-        float mx = pr[0] > pr[1] ? pr[0] : pr[1];
-        float e0 = mhppo_expf(pr[0] - mx), e1 = mhppo_expf(pr[1] - mx);
-        float sm = e0 + e1;
-        ad[i * P + p] = (e1 / sm > e0 / sm) ? 1 : 0;  // torch.argmax: first maximum
+        float p0, p1;
+        softmax_pair<LibmRollout>(pr[0], pr[1], p0, p1);
+        ad[i * P + p] = (p1 > p0) ? 1 : 0;  // torch.argmax: first maximum
       }
   }
   const size_t te = (size_t)t * N + e;
@@ -290,8 +289,7 @@ __global__ void __launch_bounds__(TPB) k_eval_step(Cfg c, Bufs eb, mhppo_mlp mc,
         float out;
         mlp_forward<NF_C, 1>(wait ? Ww : Wc, NF_C, f, &out);
         const mhppo_mlp &m = wait ? mw : mc;
-        float tt = mhppo_tanhf(out) * m.std;
-        cand = (double)(tt + m.mean);
+        cand = (double)finish_cont<LibmRollout>(out, m.mean, m.std);
       }
       if (cand < a) a = cand;  // Python min keeps the first on ties (:205-206)
       double lim = (10.0 - (double)f[0]) / c.dt;

@@ -1,6 +1,6 @@
 """ctypes wrapper of tools/libhostfwd.so: the batched head forward and the PPO diagnostics'
 per-row terms compiled for the CPU from the device source (csrc/rollout_dev.h mlp_forward,
-csrc/mlp_infer_terms.h).  numpy in, numpy out."""
+csrc/mlp_infer_terms.h), and the heads' per-row arithmetic of csrc/ppo_heads.h.  numpy in, numpy out."""
 import ctypes
 import os
 
@@ -20,7 +20,14 @@ I64, U64 = ctypes.c_int64, ctypes.c_uint64
 for _name, _args in (("hf_mvn_sample", [P, P, I64, P]), ("hf_surr_and_grad", [P, P, I64, P, P]),
                      ("hf_surr_and_grad_fd", [P, P, P, I64, P, P]), ("hf_t_minimum", [P, P, I64, P]),
                      ("hf_philox_words", [U64, U64, I64, P]), ("hf_philox_uniform", [U64, U64, I64, P]),
-                     ("hf_philox_normal", [U64, U64, I64, P])):
+                     ("hf_philox_normal", [U64, U64, I64, P]),
+                     ("hf_finish_cont", [ctypes.c_int, P, F, F, I64, P, P]), ("hf_softmax_pair", [ctypes.c_int, P, I64, P]),
+                     ("hf_cat_normalise", [P, I64, P, P]), ("hf_cat_clamp", [P, I64, P]),
+                     ("hf_adv_moments", [P, ctypes.c_double, P]), ("hf_adv_normalised", [P, F, F, I64, P]),
+                     ("hf_cont_logp_x", [P, P, I64, P, P]),
+                     ("hf_choice_term", [P, P, P, P, ctypes.c_double, I64, P, P]),
+                     ("hf_cont_row", [ctypes.c_int, P, F, F, P, P, P, ctypes.c_double, I64, P, P]),
+                     ("hf_choice_row", [P, P, P, P, ctypes.c_double, ctypes.c_int, I64, P, P])):
     getattr(L, _name).restype = None
     getattr(L, _name).argtypes = _args
 L.hf_diag_n.restype = ctypes.c_int
@@ -123,3 +130,81 @@ def philox_normal(seed, ctr0, n):
     out = np.zeros(n, np.float32)
     L.hf_philox_normal(int(seed) & _M64, int(ctr0) & _M64, n, _p(out))
     return out
+
+
+# ---- csrc/ppo_heads.h (update=True: the LibmUpdate flavour with the host's libm; False: LibmRollout)
+def finish_cont(z, mean, std, update):
+    """(tanh(z) * std + mean, tanh(z))"""
+    z = _f32(z)
+    out, t = np.zeros(z.shape, np.float32), np.zeros(z.shape, np.float32)
+    L.hf_finish_cont(int(update), _p(z), float(mean), float(std), z.size, _p(out), _p(t))
+    return out, t
+
+
+def softmax_pair(z, update):
+    z = _f32(z)
+    p = np.zeros(z.shape, np.float32)
+    L.hf_softmax_pair(int(update), _p(z), z.shape[0], _p(p))
+    return p
+
+
+def cat_normalise(p):
+    """(pn [M, 2], p0 + p1 [M])"""
+    p = _f32(p)
+    pn, sp = np.zeros(p.shape, np.float32), np.zeros(p.shape[0], np.float32)
+    L.hf_cat_normalise(_p(p), p.shape[0], _p(pn), _p(sp))
+    return pn, sp
+
+
+def cat_clamp(pn):
+    pn = _f32(pn)
+    out = np.zeros(pn.shape, np.float32)
+    L.hf_cat_clamp(_p(pn), pn.size, _p(out))
+    return out
+
+
+def adv_moments(stats, m_global):
+    """(meanf, stdf) as float32 scalars from stats = (sum A, sum A^2)"""
+    stats, out = _f64(stats), np.zeros(2, np.float32)
+    L.hf_adv_moments(_p(stats), float(m_global), _p(out))
+    return out[0], out[1]
+
+
+def adv_normalised(a, meanf, stdf):
+    a = _f32(a)
+    out = np.zeros(a.shape, np.float32)
+    L.hf_adv_normalised(_p(a), float(meanf), float(stdf), a.size, _p(out))
+    return out
+
+
+def cont_logp_x(act, mu):
+    """(logp, x) of the update's float64-difference form"""
+    act, mu = _f32(act), _f32(mu)
+    lp, x = np.zeros(act.shape, np.float32), np.zeros(act.shape, np.float32)
+    L.hf_cont_logp_x(_p(act), _p(mu), act.size, _p(lp), _p(x))
+    return lp, x
+
+
+def choice_term(pn, old, A, w, inv_m2):
+    """(fk, dL/dpn_k) of one action per element"""
+    pn, old, A, w = _f32(pn), _f64(old), _f64(A), _f64(w)
+    fk, dlp = np.zeros(pn.shape, np.float64), np.zeros(pn.shape, np.float64)
+    L.hf_choice_term(_p(pn), _p(old), _p(A), _p(w), float(inv_m2), pn.size, _p(fk), _p(dlp))
+    return fk, dlp
+
+
+def cont_row(y, mean, std, act, lp_old, A, inv_m, fd):
+    """The continuous actor's row (f [M] float64, dL/dy [M] float32); fd: the split-precision form."""
+    y, act, lp_old, A = _f32(y), _f32(act), _f32(lp_old), _f32(A)
+    f, dy = np.zeros(y.shape, np.float64), np.zeros(y.shape, np.float32)
+    L.hf_cont_row(int(fd), _p(y), float(mean), float(std), _p(act), _p(lp_old), _p(A), float(inv_m), y.size, _p(f),
+                  _p(dy))
+    return f, dy
+
+
+def choice_row(y, lp_old, A, w, inv_m2, skip_zero):
+    """The choice actor's row from y [M, 2] with weights w [M, 2]: (f [M] float64, dL/dy [M, 2] float32)."""
+    y, lp_old, A, w = _f32(y), _f32(lp_old), _f32(A), _f64(w)
+    f, dy = np.zeros(y.shape[0], np.float64), np.zeros(y.shape, np.float32)
+    L.hf_choice_row(_p(y), _p(lp_old), _p(A), _p(w), float(inv_m2), int(skip_zero), y.shape[0], _p(f), _p(dy))
+    return f, dy
