@@ -594,6 +594,37 @@ typedef struct mhppo_adam_net {
 } mhppo_adam_net;
 int mhppo_adam_clip(const mhppo_adam_net *nets, int32_t n_nets, double max_norm, double *norms, void *stream);
 
+/* ---- the minibatch shuffle (csrc/batch_shuffle.hip, csrc/batch_shuffle.h; opt-in, beyond the
+ * reference, whose epochs are full-batch) ---- */
+
+/* Destination row i is source row perm(key, M, i), for X [M, n_in] float32 (n_in 1 .. 64) and the
+ * three 4-byte columns act, logp, ret [M]; perm is a stateless keyed bijection of [0, M): nothing
+ * is drawn, sorted or kept between calls, the same (key, M) gives the same rows on any stream.
+ *   h = max(1, ceil(bitlen(M - 1) / 2)), mask = 2^h - 1   (the walk domain 4^h is >= M, < 4 M for M >= 2)
+ *   round keys k_0 .. k_7: the four Philox-4x32-10 words of counter 0 under `key` (the noise's
+ *     block and key layout, mhppo_philox_uniform), then those of counter 1
+ *   one pass over x: (L, R) = (x >> h, x & mask); for r = 0 .. 7: (L, R) <- (R, L ^ (fmix32(R ^ k_r) & mask));
+ *     x = L << h | R;  fmix32 is the murmur3 finaliser (^= >> 16, *= 0x85EBCA6B, ^= >> 13, *= 0xC2B2AE35, ^= >> 16)
+ *   perm(key, M, i): the pass applied to i, and again while the result is >= M (cycle-walk)
+ * The act column is copied bitwise (float32 of the continuous heads, int32 of the choice head), as
+ * are logp, ret and X: NaN payloads and signed zeros survive.
+ * K >= 1 is the number of slices the caller will cut the shuffled batch into: slice j holds the
+ * rows [b_j, b_{j+1}), b_j = 4 floor(j ceil(M / 4) / K) for j < K, b_K = M: every slice starts at a
+ * multiple of 4 rows (16-byte aligned for the train kernels whatever n_in is); slices are empty
+ * when M < 4 K.  K matters to `counts` alone.
+ * counts: NULL, or float64 [K][2]; act is then int32 and counts[j] = (the rows of slice j with
+ * act == 0, with act == 1), folded in csrc/block_prims.h's fixed order by one block per slice in a
+ * second launch, no atomics (M <= 2^30 with counts).
+ * M == 0 launches nothing; counts, if given, is zeroed.  M <= 2^31 - 1.
+ * Sources need 4-byte alignment only (a bucket that starts at any row of a shared buffer);
+ * destinations must be 16-byte aligned.
+ * MHPPO_EINVAL, nothing written: n_in outside 1 .. 64, K < 1, M out of range, and for M > 0 a NULL
+ * source or destination, a source not 4-byte or a destination not 16-byte aligned, a source range
+ * that overlaps a destination range. */
+int mhppo_batch_shuffle(int32_t n_in, int64_t M, const float *X, const void *act, const float *logp,
+                        const float *ret, uint64_t key, int32_t K, float *X_out, void *act_out, float *logp_out,
+                        float *ret_out, double *counts, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

@@ -118,6 +118,7 @@ _SIGS = {
     "mhppo_eval_stats_row": (I32, [P, P, I32, I32, P, P]),
     "mhppo_eval_stats_fold": (I32, [P, P, P, P]),
     "mhppo_adam_clip": (I32, [P, I32, F64, P, P]),
+    "mhppo_batch_shuffle": (I32, [I32, I64, P, P, P, P, U64, I32, P, P, P, P, P, P]),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }
@@ -197,6 +198,14 @@ def adam_clip(nets, n_nets, max_norm, norms, stream):
     with max_grad_norm set), so a run with the knob off can be shown never to reach it.  `nets`: a
     ctypes array of AdamNet (host), `norms` / `stream`: addresses."""
     return check(lib().mhppo_adam_clip(ctypes.addressof(nets), n_nets, max_norm, norms, stream))
+
+
+def batch_shuffle(n_in, M, X, act, logp, ret, key, K, X_out, act_out, logp_out, ret_out, counts, stream):
+    """mhppo_batch_shuffle, checked: the one place the entry point is called from (mhppo.shuffle
+    .shuffle_batch), so a run without minibatches can be shown never to reach it.  Addresses (or
+    None), sizes and the 64-bit key."""
+    return check(lib().mhppo_batch_shuffle(n_in, M, X, act, logp, ret, int(key) & 0xFFFFFFFFFFFFFFFF, K, X_out,
+                                           act_out, logp_out, ret_out, counts, stream))
 
 
 def ptr(t):

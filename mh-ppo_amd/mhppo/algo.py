@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _lib, ppo
+from . import _lib, ppo, shuffle
 from .env import VecCrosswalk
 from .models import Model_PPO
 from .rollout import RolloutGPU, bucket_segments
@@ -269,6 +269,17 @@ class Algo_PPO:
         # launch (mhppo.adam.adam_clip_steps); inf clips nothing and only records the norms
         # (self.grad_norms).  A constructor argument, as gae_lambda is: nothing of it is checkpointed.
         self.max_grad_norm = None
+        # minibatch updates (beyond the reference, whose ten epochs per head are full-batch): None =
+        # off, update() makes exactly the calls it always did; an integer K >= 1 runs every epoch as K
+        # minibatch steps per head on a fresh keyed shuffle of the head's batch
+        # (mhppo.ppo.train_minibatches: each step is train_epoch on a slice, so every optimiser takes
+        # 10 K steps per iteration and the advantage is normalised per minibatch).  The shuffle's key
+        # is mhppo.shuffle.shuffle_key(rollout.seed, the iteration the batch was collected in, epoch,
+        # head index, the shard's first global env id): no generator state, so nothing of it is
+        # checkpointed and a resumed run draws the same minibatches.  A constructor argument, as
+        # gae_lambda is.  Under data parallelism every rank shuffles its own shard: a different draw
+        # of minibatches than one process on all envs.
+        self.minibatches = None
         for k, v in hyperparameters.items():
             setattr(self, k, v)
         if self.max_grad_norm is not None:
@@ -283,28 +294,46 @@ class Algo_PPO:
             if not 0.0 <= float(self.gamma) <= 1.0:
                 raise ValueError(f"gae_lambda needs gamma in [0, 1], not {self.gamma!r}")
             self.gae_lambda = lam
+        if self.minibatches is not None:
+            k = self.minibatches
+            if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+                raise ValueError(f"minibatches must be None or an integer >= 1, not {k!r}")
 
     def update(self):
         """10 epochs of cross+wait, then 10 epochs of choice (:868-882) on the collected batch,
         run as 10 joint epochs of the three independent heads in one pipeline of 11 steps
         (mhppo.ppo.train_epochs: same results, two collectives per step under data parallelism).
         The global row counts and choice action counts take one all-reduce and one host sync per
-        iteration."""
+        iteration.  With minibatches=K the ten epochs run as 10 K minibatch steps instead
+        (mhppo.ppo.train_minibatches); the heads' global slice sizes travel in the same all-reduce."""
         r = self.rollout
         dev = self.venv.device
         c, w, d = r.cross, r.wait, r.choice
+        K = getattr(self, "minibatches", None)
         with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
             counts = d.get("counts")  # queued with the bucketing, before its host sync
             if counts is None:
                 counts = torch.stack([(d["act"] == 0).sum(), (d["act"] == 1).sum()]).to(torch.float64)
             if ppo._dp():  # global row counts: one all-reduce and one host sync
-                loc = torch.cat([torch.tensor([c["ret"].numel(), w["ret"].numel(), d["ret"].numel()],
-                                              dtype=torch.float64, device=dev), counts])
+                rows = [c["ret"].numel(), w["ret"].numel(), d["ret"].numel()]
+                if K is not None:  # followed by the three heads' local slice sizes, [3, K]
+                    for n in rows[:3]:
+                        b = shuffle.slice_bounds(n, K)
+                        rows += [b[j + 1] - b[j] for j in range(K)]
+                loc = torch.cat([torch.tensor(rows, dtype=torch.float64, device=dev), counts])
                 ppo._allreduce_(loc)
-                m_c, m_w, m_d = loc[:3].tolist()
-                counts = loc[3:5]
+                n = len(rows)
+                slice_m = None
+                if K is None:
+                    m_c, m_w, m_d = loc[:3].tolist()
+                else:
+                    host = loc[:n].tolist()
+                    m_c, m_w, m_d = host[:3]
+                    slice_m = {k: host[3 + i * K:3 + (i + 1) * K] for i, k in enumerate(("cross", "wait", "choice"))}
+                counts = loc[n:n + 2]
             else:  # the local counts are the global ones, known on the host: no sync
                 m_c, m_w, m_d = float(c["ret"].numel()), float(w["ret"].numel()), float(d["ret"].numel())
+                slice_m = None  # the local slice sizes are the global ones: train_minibatches forms them
             heads, names = [], []
             # the reference trains a continuous head only on a non-empty batch (:869, :874); its choice
             # batch is never empty (>= 1 existing car per episode; it would raise there)
@@ -317,7 +346,9 @@ class Algo_PPO:
                                           per_row=kind == "d" and self.fix_choice_loss, exact=self.exact_f32))
                     names.append(name)
             clip = getattr(self, "max_grad_norm", None)
-            if clip is None:
+            if K is not None:
+                losses = self._update_minibatches(heads, names, K, clip, slice_m) if heads else None
+            elif clip is None:
                 losses = ppo.train_epochs(heads, 10, self.grad_bucket) if heads else None
             else:
                 losses, norms = ppo.train_epochs(heads, 10, self.grad_bucket, clip) if heads else (None, None)
@@ -328,9 +359,29 @@ class Algo_PPO:
             div = {"cross": (m_c, m_c), "wait": (m_w, m_w), "choice": (m_d * m_d, m_d)}
             if self.fix_choice_loss:
                 div["choice"] = (m_d, m_d)
-            self.last_losses = {k: (float(a.item()) / div[k][0], float(b.item()) / div[k][1])
-                                for k, (a, b) in zip(names, losses)}
+            if K is not None:
+                # the losses of each head's last minibatch step, over that step's m (a head in
+                # `heads` has rows, so it is trained in at least one step)
+                div = {k: ((m * m if k == "choice" and not self.fix_choice_loss else m), m)
+                       for k, (_, _, m) in zip(names, losses)}
+            self.last_losses = {k: (float(x[0].item()) / div[k][0], float(x[1].item()) / div[k][1])
+                                for k, x in zip(names, losses)}
         return m_c, m_w, m_d
+
+    def _update_minibatches(self, heads, names, K, clip, slice_m):
+        """update() with minibatches=K: mhppo.ppo.train_minibatches over the iteration's heads, the
+        shuffle keyed by mhppo.shuffle.shuffle_key (the batch was collected in iteration
+        rollout.iteration - 1: iterations_rand has counted it already)."""
+        r, v = self.rollout, self.venv
+        env0 = int(getattr(v, "env_id_offset", getattr(getattr(v, "cfg", None), "env_id_offset", 0)))
+        seed, it = int(r.seed), int(r.iteration) - 1
+        idx = [shuffle.HEAD_INDEX[n] for n in names]
+        res = ppo.train_minibatches(heads, 10, K, lambda e, i: shuffle.shuffle_key(seed, it, e, idx[i], env0),
+                                    self.grad_bucket, clip, None if slice_m is None else [slice_m[n] for n in names])
+        if clip is None:
+            return res
+        self._norms_dev = (res[1], names)
+        return res[0]
 
     def evaluate(self, nbr_episodes, choix=False):
         """(:738-747) rollout.reset() then the deterministic iterations; with N envs every env

@@ -612,6 +612,133 @@ def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None):
     return [tuple(o) for o in out]
 
 
+# ------------------------------------------------------------- minibatches (opt-in)
+
+class _SliceHead:
+    """What the pass helpers read of a Head, for one slice: the nets and the slice's GLOBAL row count."""
+
+    def __init__(self, h, m):
+        self.actor, self.critic, self.kind, self.m = h.actor, h.critic, h.kind, float(m)
+
+
+class _SlicePlan:
+    """Rows [b0, b1) of a _HeadPlan on the shuffled buffers: the same nets, the tensors as views
+    (what the CPU doubles read) and the integer addresses offset by b0 rows (what the launchers
+    read); b0 is a multiple of 4 rows, so X stays 16-byte aligned.  counts: the slice's global
+    (n0, n1), two doubles of the call's counts buffer, or None."""
+
+    def __init__(self, p, b0, b1, counts):
+        for k in ("akind", "n_in", "wa", "wc", "ga", "gc", "mean", "std", "flags", "keep"):
+            setattr(self, k, getattr(p, k))
+        self.pair = False
+        self.M = b1 - b0
+        self.obs, self.ret, self.V, self.lp = p.obs[b0:b1], p.ret[b0:b1], p.V[b0:b1], p.lp[b0:b1]
+        self.act = None if p.act is None else p.act[b0:b1]
+        self.counts = counts
+        self.x, self.r, self.v, self.l = p.x + 4 * self.n_in * b0, p.r + 4 * b0, p.v + 4 * b0, p.l + 4 * b0
+        self.a = None if p.a is None else p.a + 4 * b0
+        self.cn = _addr(counts)
+
+
+def train_minibatches(heads, n_epochs, K, key_fn, bucket=None, max_grad_norm=None, slice_m=None):
+    """n_epochs epochs of K minibatch steps per head (opt-in, Algo_PPO(minibatches=K); the reference
+    and train_epochs run full-batch epochs).  Per epoch every head's batch is shuffled once, from the
+    ORIGINAL tensors into the call's one shuffled copy, under key_fn(epoch, i) (i: the head's
+    position in `heads`; mhppo.shuffle: a stateless keyed permutation, mhppo_batch_shuffle on the
+    GPU); the copy is cut into K slices (mhppo.shuffle.slice_bounds) and step j of the epoch is
+    EXACTLY train_epoch on slice j of every head: critic passes -> one all-reduce of the advantage
+    sums -> actor passes -> gradient all-reduce -> Adam (clipped with max_grad_norm).  So m_global
+    of a pass is the slice's global row count, the advantage is normalised per minibatch with the
+    critic as it stands at that step, and the choice head gets its slice's global (n0, n1) (from
+    the shuffle's per-slice counts), or its actions with the per-row loss.  Each optimiser steps
+    n_epochs * K times, less the steps at which its head's slice is globally empty (M < 4 K): such
+    a head is left out of the step, as update() leaves out an empty head; a locally empty slice
+    runs with M == 0 and joins every collective.
+    The driver is sequential on purpose: train_epochs' fused pair launch needs the actor pass and
+    the next critic pass on the same rows, which holds for no two consecutive minibatches.
+    The kernels are reached through _critic_pass / _actor_pass alone, one launcher call per pass
+    with integer addresses resolved once per call (_HeadPlan on the shuffled copy, _SlicePlan).
+    Data parallel: every rank shuffles its own shard and slices it by its local row count, so
+    slice j is the union of the ranks' local slices j: a different draw of minibatches than one
+    process on all envs would make (each is a uniform-looking sample of its shard; the results are
+    not comparable run to run across world sizes, as the full-batch update's are).  Collectives: one
+    all-reduce of the [H, K] local slice sizes per call (none when the caller passes slice_m, the
+    GLOBAL sizes: update() joins it with its counts all-reduce), one of the choice heads' counts
+    per epoch, and train_epoch's two per step.
+    Returns per head (actor loss sum, critic loss sum, m) of the last step it was trained in (this
+    rank's sums, float64 [1] tensors; m that step's global row count; None for a head never
+    trained); with max_grad_norm also norms, float64 [n_epochs * K, 2 H] on the device in
+    train_epochs' column layout (column j head j's critic, H + j its actor), NaN where a net was
+    not stepped."""
+    from . import shuffle
+    H, K = len(heads), int(K)
+    if K < 1:
+        raise ValueError(f"K must be >= 1, not {K}")
+    dev = heads[0].obs.device
+    with _on_device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+        dp = _dp()
+        n_choice = sum(1 for h in heads if h.kind != "c" and not h.per_row)
+        counts_all = torch.zeros(max(1, n_choice), K, 2, dtype=torch.float64, device=dev)
+        srcs, dsts, cnts, plans = [], [], [], []
+        for h in heads:
+            fl = h.kind == "c" or h.per_row  # the actions as the train kernel reads them, or int32 for the counts
+            act = h.act.float().contiguous() if fl else h.act.to(torch.int32).contiguous()
+            src = (h.obs.float().contiguous(), act, h.logp.float().contiguous(), h.ret.float().contiguous())
+            dst = tuple(torch.empty_like(t) for t in src)
+            cnt = None if fl else counts_all[sum(1 for c in cnts if c is not None)]
+            srcs.append(src), dsts.append(dst), cnts.append(cnt)
+            plans.append(_HeadPlan(Head(h.kind, h.actor, h.critic, h.opt_actor, h.opt_critic, *dst, h.m, cnt,
+                                        h.per_row, h.exact)))
+        bounds = [shuffle.slice_bounds(p.M, K) for p in plans]
+        if slice_m is None:
+            slice_m = [[float(b[j + 1] - b[j]) for j in range(K)] for b in bounds]
+            if dp:  # one all-reduce and one host read per call
+                slice_m = _allreduce_(torch.tensor(slice_m, dtype=torch.float64, device=dev)).tolist()
+        sp = [[_SlicePlan(p, b[j], b[j + 1], None if c is None else c[j]) for j in range(K)]
+              for p, b, c in zip(plans, bounds, cnts)]
+        sh = [[_SliceHead(h, slice_m[i][j]) for j in range(K)] for i, h in enumerate(heads)]
+        norms = None
+        if max_grad_norm is not None:
+            norms = torch.full((n_epochs * K, 2 * H), math.nan, dtype=torch.float64, device=dev)
+        all_sums = torch.zeros(n_epochs * K, 2 * H, 3, dtype=torch.float64, device=dev)  # critic rows, actor rows
+        out = [None] * H
+        for e in range(n_epochs):
+            for i in range(H):
+                shuffle.shuffle_batch(srcs[i], dsts[i], key_fn(e, i), K, cnts[i])
+            if n_choice:
+                _allreduce_(counts_all)
+            for j in range(K):
+                on = [i for i in range(H) if slice_m[i][j] > 0]
+                if not on:
+                    continue
+                sums = all_sums[e * K + j]
+                for i in on:
+                    _critic_pass(sp[i][j], sh[i][j], sums[i], st)
+                stats = None
+                if dp:  # the all-reduce needs one span
+                    stats = sums[:H, 1:3].reshape(-1).contiguous()
+                    _allreduce_(stats)
+                for i in on:
+                    _actor_pass(sp[i][j], sh[i][j], stats[2 * i:2 * i + 2] if dp else sums[i, 1:3], sums[H + i], st)
+                    out[i] = (sums[H + i, 0:1], sums[i, 0:1], slice_m[i][j])
+                nout = tmp = None
+                if norms is not None:
+                    if len(on) == H:
+                        nout = norms[e * K + j]
+                    else:
+                        nout = tmp = torch.empty(2 * len(on), dtype=torch.float64, device=dev)
+                # train_epochs' order within a step: the critics, then the actors
+                _reduce_and_step([n for i in on for n in (heads[i].actor, heads[i].critic)],
+                                 [heads[i].opt_critic for i in on] + [heads[i].opt_actor for i in on], bucket,
+                                 max_grad_norm, nout)
+                if tmp is not None:
+                    norms[e * K + j, [i for i in on] + [H + i for i in on]] = tmp
+    if norms is not None:
+        return out, norms
+    return out
+
+
 def train_model_c(actor, critic, opt_actor, opt_critic, obs, act, logp_old, ret, m_global, exact=False):
     """One full-batch epoch of Algo_PPO.train_model_c (:778-815) for one head.
     Returns this rank's (actor, critic) loss sums (float64 tensors)."""
