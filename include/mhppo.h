@@ -625,6 +625,49 @@ int mhppo_batch_shuffle(int32_t n_in, int64_t M, const float *X, const void *act
                         const float *ret, uint64_t key, int32_t K, float *X_out, void *act_out, float *logp_out,
                         float *ret_out, double *counts, void *stream);
 
+/* ---- stateless policy inference (csrc/policy_infer.hip, csrc/policy_rule.h; opt-in, beyond the
+ * reference, whose only way from the heads to an action is Env_rollout.iterations :152-252 on its own
+ * env) ---- */
+
+/* The deterministic policy of mhppo_eval_step as a function of observation rows: no env handle, the
+ * rows may come from anywhere (another simulator, a recorded trajectory, a grid).  `cfg` names the
+ * observation layout and the constants of the rule (variant, nb_car, nb_ped, nb_lines, dt, car_b);
+ * n_envs, the seeds and flags are ignored.  It gets mhppo_env_create's variant and shape checks.
+ * The calls run on the current device.
+ *
+ * The rule (csrc/policy_rule.h), per row o with S slots and P pedestrians:
+ *   decide  a_d[i][p] = (p1 > p0) of softmax(choice(obs_car_ped_d(o, i, p)))   (the first maximum)
+ *   act     for each slot i:  a = car_b[1][0];  for p = 0 .. P - 1:
+ *             f = obs_car_ped(o, i, p)                                          (13 features)
+ *             cand = f[7] != 0 ? max(car_b[0][0], min(car_b[1][0], (10 - f[0]) / dt))    (float64)
+ *                              : (double)(tanh(head(f)) * std + mean), head = wait if 2 a_d[i][p] - 1 > 0
+ *                                                                             else cross
+ *             if (cand < a) a = cand;  lim = (10 - (double)f[0]) / dt;  if (lim < a) a = lim
+ *           actions[i] = a
+ *   lights  actions[S + i] = 2 a_d.flat[i] - 1: the FLAT index i into the row's [S, P] block, not
+ *           [i][0] (the reference's quirk, :188, :210; the two differ when P > 1)
+ * Comparisons with NaN are false: a NaN head output changes nothing and is reported nowhere.
+ * Every head output is bit for bit mhppo_mlp_forward's for the same feature row, and actions are
+ * bit for bit what mhppo_eval_step hands its env step for the same o and a_d.  When a choice is
+ * re-decided is the caller's schedule (mhppo.policy.PolicySession restates mhppo_eval_step's).
+ * Both launches walk 32-triple tiles on f32 MFMA; the feature rows are built in LDS from the
+ * observation rows and never written to memory.  No atomics, nothing depends on the grid: the
+ * same call gives the same bits on any stream.  M == 0 launches nothing and touches nothing.
+ * obs needs 4-byte alignment only. */
+
+/* out = (obs_dim, S, P, choice_dim) of a config; no device is touched. */
+int mhppo_policy_dims(const mhppo_env_cfg *cfg, int32_t out[4]);
+/* obs float32 [M, obs_dim]; a_d int32 [M, S, P]; probs float32 [M, S, P, 2] or NULL.
+ * MHPPO_EINVAL: a refused config, actor_choice not kind 2 with n_in == choice_dim (<= 64) and n_out 2,
+ * a NULL pointer, M < 0. */
+int mhppo_policy_decide(const mhppo_env_cfg *cfg, const mhppo_mlp *actor_choice, const float *obs, int64_t M,
+                        int32_t *a_d, float *probs, void *stream);
+/* actions float64 [M, 2S] = [acc_0 .. acc_{S-1}, light_0 .. light_{S-1}], the layout mhppo_env_step takes.
+ * MHPPO_EINVAL: a refused config, nb_ped > 32 (a slot's pedestrians share one tile), an actor not
+ * kind 1 with 13 inputs and 1 output, a NULL pointer, M < 0. */
+int mhppo_policy_act(const mhppo_env_cfg *cfg, const mhppo_mlp *actor_cross, const mhppo_mlp *actor_wait,
+                     const float *obs, const int32_t *a_d, int64_t M, double *actions, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

@@ -119,6 +119,9 @@ _SIGS = {
     "mhppo_eval_stats_fold": (I32, [P, P, P, P]),
     "mhppo_adam_clip": (I32, [P, I32, F64, P, P]),
     "mhppo_batch_shuffle": (I32, [I32, I64, P, P, P, P, U64, I32, P, P, P, P, P, P]),
+    "mhppo_policy_dims": (I32, [ctypes.POINTER(EnvCfg), P]),
+    "mhppo_policy_decide": (I32, [ctypes.POINTER(EnvCfg), ctypes.POINTER(Mlp), P, I64, P, P, P]),
+    "mhppo_policy_act": (I32, [ctypes.POINTER(EnvCfg), ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, I64, P, P]),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }

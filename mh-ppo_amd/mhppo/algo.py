@@ -405,6 +405,13 @@ class Algo_PPO:
         ppo._allreduce_(sums)
         return stats_from_sums(sums, self.venv.nb_car)
 
+    def policy(self):
+        """The deterministic policy of evaluate() as a function of observation rows (mhppo.policy
+        .Policy; opt-in, beyond the reference) on the live actors: it reads their weights at every
+        call, so it tracks training."""
+        from .policy import Policy
+        return Policy.from_env(self.venv, self.actor_net_cross, self.actor_net_wait, self.actor_net_choice)
+
     def get_average(self, states):
         """The paper cell's evaluation statistics (get_average, :1550-1675; CO2 leg excluded)
         over `states`, the observations evaluate() returned (mhppo.stats)."""
