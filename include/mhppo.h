@@ -668,6 +668,56 @@ int mhppo_policy_decide(const mhppo_env_cfg *cfg, const mhppo_mlp *actor_choice,
 int mhppo_policy_act(const mhppo_env_cfg *cfg, const mhppo_mlp *actor_cross, const mhppo_mlp *actor_wait,
                      const float *obs, const int32_t *a_d, int64_t M, double *actions, void *stream);
 
+/* ---- stochastic policy sampling (csrc/policy_infer.hip, csrc/policy_sample_rule.h; opt-in) ---- */
+
+/* The training policy of the collector (mhppo_rollout_begin / _policy / _sample_env) as a function of
+ * observation rows: no env handle, nothing written but the outputs named here.  `cfg`, the device and
+ * obs's alignment are mhppo_policy_decide's.
+ *
+ * The rule (csrc/policy_sample_rule.h), per row o:
+ *   decide  (slot i, ped p): (p0, p1) = softmax(choice(obs_car_ped_d(o, i, p))); n = p / (p0 + p1);
+ *             a_d = u >= n[0] (or the forced value); logp_d = logf(clamp(n[a_d], eps, 1 - eps))
+ *           (slot i): closest = closest_ped_d(o, i); exist = the car's exist field != 0 (scalable), else 1
+ *   act     (slot i): loc = 2.0f, sel = 0; for p = 0 .. P - 1 (scalable: pedestrians whose exist field
+ *             is 0 take no part): out = tanh(head(obs_car_ped(o, i, p))) * std + mean, head = wait if
+ *             2 a_d[i][p] - 1 > 0 else cross; loc = torch.minimum(loc, out); if (out == loc) sel = p
+ *           a = loc + L eps; logp = MVN(loc, 0.5).log_prob(a)                          (float32)
+ *           actions[i] = a; actions[S + i] = 2 a_d[i][closest[i]] - 1 (a closest outside [0, P): 0)
+ *           feat_c[i] = obs_car_ped(o, i, sel)
+ * No left-lane override and no speed cap.  An absent car slot of the scalable variant (exist 0) is
+ * computed as any other slot, as the collector does (its action reaches the env step); the collector
+ * keeps no record of it, so its act, logp and feat_c are the caller's to mask with `exist`.  status (uint32 [1] or NULL; only ever OR-ed into): bit 1 for NaN
+ * choice probabilities, bit 2 for a NaN loc, as mhppo_rollout_check reads them.
+ * On present slots every output is bit for bit what the collector records for the same row, weights
+ * and noise (logp_d within the device logf's rounding of the host's).
+ *
+ * mhppo_policy_noise: `tape` (decide: u float32 [M, S, P]; act: eps float32 [M, S]) or, for decide,
+ * `forced` (int32 [M, S, P]: the decisions themselves) when set; with both NULL the draw is made in
+ * the kernel, Philox-4x32-10 under `key` at the collector's counters (mhppo_philox_uniform /
+ * _normal as RolloutGPU.draw_noise calls them): row r is env first_env + r,
+ *   u(r, i, p)   counter (first_env + r) S P + i P + p
+ *   eps(r, i)    counter (t + 1) 2^40 + (first_env + r) S + i
+ * and key = seed * 1000003 + iteration (mod 2^64). */
+typedef struct mhppo_policy_noise {
+  const float *tape;
+  const int32_t *forced;
+  uint64_t key, first_env;
+  int64_t t; /* act, Philox form: the step (>= 0) */
+} mhppo_policy_noise;
+
+/* a_d int32, logp_d float32 [M, S, P]; probs float32 [M, S, P, 2], feat_d float32 [M, S, P, choice_dim]
+ * and status may be NULL (their stores are skipped); closest int32, exist uint8 [M, S].
+ * MHPPO_EINVAL: as mhppo_policy_decide; a NULL noise, or one with both tape and forced. */
+int mhppo_policy_sample_decide(const mhppo_env_cfg *cfg, const mhppo_mlp *actor_choice, const float *obs, int64_t M,
+                               const mhppo_policy_noise *noise, int32_t *a_d, float *logp_d, float *probs,
+                               float *feat_d, int32_t *closest, uint8_t *exist, uint32_t *status, void *stream);
+/* actions float64 [M, 2S]; act, logp float32 [M, S]; feat_c float32 [M, S, 13] and status may be NULL.
+ * MHPPO_EINVAL: as mhppo_policy_act; a NULL noise, one with forced set, or the Philox form with t < 0. */
+int mhppo_policy_sample_act(const mhppo_env_cfg *cfg, const mhppo_mlp *actor_cross, const mhppo_mlp *actor_wait,
+                            const float *obs, const int32_t *a_d, const int32_t *closest, int64_t M,
+                            const mhppo_policy_noise *noise, double *actions, float *act, float *logp, float *feat_c,
+                            uint32_t *status, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

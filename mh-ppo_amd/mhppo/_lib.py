@@ -48,6 +48,10 @@ class EvalBufs(ctypes.Structure):
                 ("rews_d", P), ("waiting", P), ("saved", P), ("T", I32), ("reserved", I32)]
 
 
+class PolicyNoise(ctypes.Structure):  # mhppo_policy_noise
+    _fields_ = [("tape", P), ("forced", P), ("key", U64), ("first_env", U64), ("t", I64)]
+
+
 class AdamSeg(ctypes.Structure):  # mhppo_adam_seg
     _fields_ = [("param", P), ("grad", P), ("exp_avg", P), ("exp_avg_sq", P), ("step", P), ("n", I64)]
 
@@ -122,6 +126,10 @@ _SIGS = {
     "mhppo_policy_dims": (I32, [ctypes.POINTER(EnvCfg), P]),
     "mhppo_policy_decide": (I32, [ctypes.POINTER(EnvCfg), ctypes.POINTER(Mlp), P, I64, P, P, P]),
     "mhppo_policy_act": (I32, [ctypes.POINTER(EnvCfg), ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, I64, P, P]),
+    "mhppo_policy_sample_decide": (I32, [ctypes.POINTER(EnvCfg), ctypes.POINTER(Mlp), P, I64,
+                                         ctypes.POINTER(PolicyNoise)] + [P] * 8),
+    "mhppo_policy_sample_act": (I32, [ctypes.POINTER(EnvCfg), ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, I64,
+                                      ctypes.POINTER(PolicyNoise)] + [P] * 6),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }

@@ -6,6 +6,11 @@ simulator, a recorded trajectory, a grid of observations for a decision map) on 
 (Env_rollout.iterations, Coop-MH-PPO-scalable.py:152-252), bit for bit what mhppo_eval_step hands
 its env step.  `PolicySession` adds the evaluation's decision schedule for parallel streams of
 observations.  There is no CPU path.
+
+sample_decide / sample_act apply the TRAINING policy instead (mhppo_policy_sample_decide / _sample_act):
+the collector's Categorical and Gaussian draws with their log-probabilities and recorded feature rows,
+bit for bit what RolloutGPU.collect records for the same rows, weights and noise.  `SamplingSession`
+strings them into the collector's episode schedule (one decision at t = 0).
 """
 import ctypes
 
@@ -15,6 +20,28 @@ from . import _lib
 from .env import CAR_B, VARIANTS, _flat
 
 MAX_P = 32  # mhppo_policy_act: a slot's pedestrians share one 32-row tile
+_MASK64 = (1 << 64) - 1
+
+
+def noise_key(seed, iteration):
+    """The Philox key of the collector's noise for (seed, iteration) (RolloutGPU.draw_noise)."""
+    return (int(seed) * 1000003 + int(iteration)) & _MASK64
+
+
+class SampleDecision:
+    """Policy.sample_decide's result: a_d int32, logp_d float32 [M, S, P]; closest int32, exist uint8
+    [M, S]; probs float32 [M, S, P, 2] and feat_d float32 [M, S, P, choice_dim] when asked for, else None."""
+
+    def __init__(self, a_d, logp_d, closest, exist, probs=None, feat_d=None):
+        self.a_d, self.logp_d, self.closest, self.exist, self.probs, self.feat_d = a_d, logp_d, closest, exist, probs, feat_d
+
+
+class SampleAction:
+    """Policy.sample_act's result: actions float64 [M, 2S] (the layout VecCrosswalk.step takes), act and
+    logp float32 [M, S], feat_c float32 [M, S, 13] (None without want_features)."""
+
+    def __init__(self, actions, act, logp, feat_c=None):
+        self.actions, self.act, self.logp, self.feat_c = actions, act, logp, feat_c
 
 
 class Policy:
@@ -98,6 +125,89 @@ class Policy:
                                                    _lib.ptr(obs), _lib.ptr(a_d), M, _lib.ptr(out), _lib.stream_ptr()))
         return out
 
+    def _status(self, status, dev, what):
+        if status is None:
+            return None
+        if (not torch.is_tensor(status) or status.dtype != torch.int32 or status.numel() != 1 or status.device != dev
+                or not status.is_contiguous()):
+            raise ValueError(f"{what} takes status as an int32 [1] tensor on obs's device")
+        return status
+
+    def _tape(self, x, shape, dtype, dev, what, name):
+        if not torch.is_tensor(x) or x.dtype != dtype or tuple(x.shape) != shape or x.device != dev:
+            raise ValueError(f"{what} takes {name} as a {str(dtype).split('.')[-1]} {list(shape)} tensor on obs's device")
+        return x.contiguous()
+
+    def sample_decide(self, obs, u=None, forced=None, key=None, first_env=0, want_probs=False, want_features=False,
+                      status=None):
+        """The collector's Categorical draw of every (slot, pedestrian) -> SampleDecision.  Exactly one
+        noise source: u float32 [M, S, P] (a_d = u >= p(cross)), forced int32 [M, S, P] (the decisions
+        themselves), or key (noise_key(seed, iteration): Philox at the collector's counters, row r being
+        env first_env + r).  status: int32 [1] that receives bit 1 on NaN probabilities (OR-ed in; None:
+        nothing is written)."""
+        what = "Policy.sample_decide"
+        obs = self._rows(obs, what)
+        if sum(x is not None for x in (u, forced, key)) != 1:
+            raise ValueError(f"{what} takes exactly one noise source: u, forced or key")
+        M, S, P = obs.shape[0], self.n_slots, self.nb_ped
+        dev = obs.device
+        nz = _lib.PolicyNoise()
+        if u is not None:
+            u = self._tape(u, (M, S, P), torch.float32, dev, what, "u")
+            nz.tape = u.data_ptr()
+        elif forced is not None:
+            forced = self._tape(forced, (M, S, P), torch.int32, dev, what, "forced")
+            nz.forced = forced.data_ptr()
+        else:
+            nz.key, nz.first_env = int(key) & _MASK64, int(first_env) & _MASK64
+        status = self._status(status, dev, what)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = SampleDecision(e((M, S, P), torch.int32), e((M, S, P), torch.float32), e((M, S), torch.int32),
+                             e((M, S), torch.uint8), e((M, S, P, 2), torch.float32) if want_probs else None,
+                             e((M, S, P, self.choice_dim), torch.float32) if want_features else None)
+        d, keep = self.actor_choice.mlp_desc()
+        p = _lib.ptr
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mhppo_policy_sample_decide(
+                ctypes.byref(self.cfg), ctypes.byref(d), p(obs), M, ctypes.byref(nz), p(out.a_d), p(out.logp_d),
+                p(out.probs), p(out.feat_d), p(out.closest), p(out.exist), p(status), _lib.stream_ptr()))
+        return out
+
+    def sample_act(self, obs, a_d, closest, eps=None, key=None, first_env=0, t=0, want_features=True, status=None):
+        """The collector's Gaussian draw of every slot from the rows, their decisions a_d int32 [M, S, P]
+        and closest int32 [M, S] -> SampleAction.  Exactly one noise source: eps float32 [M, S] (standard
+        normals), or key (Philox at the collector's counters of step t, row r being env first_env + r).
+        status: int32 [1] that receives bit 2 on a NaN loc."""
+        what = "Policy.sample_act"
+        obs = self._rows(obs, what)
+        if sum(x is not None for x in (eps, key)) != 1:
+            raise ValueError(f"{what} takes exactly one noise source: eps or key")
+        M, S, P = obs.shape[0], self.n_slots, self.nb_ped
+        dev = obs.device
+        a_d = self._tape(a_d, (M, S, P), torch.int32, dev, what, "a_d")
+        closest = self._tape(closest, (M, S), torch.int32, dev, what, "closest")
+        nz = _lib.PolicyNoise()
+        if eps is not None:
+            eps = self._tape(eps, (M, S), torch.float32, dev, what, "eps")
+            nz.tape = eps.data_ptr()
+        else:
+            if int(t) < 0:
+                raise ValueError(f"{what}: t < 0")
+            nz.key, nz.first_env, nz.t = int(key) & _MASK64, int(first_env) & _MASK64, int(t)
+        status = self._status(status, dev, what)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        out = SampleAction(e((M, 2 * S), torch.float64), e((M, S), torch.float32), e((M, S), torch.float32),
+                           e((M, S, 13), torch.float32) if want_features else None)
+        dc, kc = self.actor_cross.mlp_desc()
+        dw, kw = self.actor_wait.mlp_desc()
+        p = _lib.ptr
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mhppo_policy_sample_act(
+                ctypes.byref(self.cfg), ctypes.byref(dc), ctypes.byref(dw), p(obs), p(a_d), p(closest), M,
+                ctypes.byref(nz), p(out.actions), p(out.act), p(out.logp), p(out.feat_c), p(status),
+                _lib.stream_ptr()))
+        return out
+
 
 class PolicySession:
     """The evaluation's decision schedule for M parallel streams of observations.
@@ -129,3 +239,36 @@ class PolicySession:
             self.a_d = torch.where(due[:, None, None], a_new, self.a_d)
         self.c_prev = c
         return pol.act(obs, self.a_d)
+
+
+class SamplingSession:
+    """The collector's episode schedule for M parallel streams, env first_env + r being stream r, under
+    the collector's Philox noise of `seed`: begin(obs, iteration) decides once from the episode's first
+    rows (the collector decides at t = 0 only), step(obs, t) -> actions [M, 2S] for step t's rows and keeps
+    that step's act, logp and feat_c.  Device ops only, no host read."""
+
+    def __init__(self, policy, M, seed=0, first_env=0):
+        self.policy, self.M, self.seed, self.first_env = policy, int(M), int(seed), int(first_env)
+        self.key = None
+        self.decision = None  # the SampleDecision in force
+        self.act = self.logp = self.feat_c = None  # the last step's records
+
+    def _check(self, obs, what):
+        if torch.is_tensor(obs) and obs.dim() == 2 and obs.shape[0] != self.M:
+            raise ValueError(f"SamplingSession.{what} takes one row per stream: [{self.M}, {self.policy.obs_dim}]")
+
+    def begin(self, obs, iteration=0, want_probs=False, want_features=False, status=None):
+        self._check(obs, "begin")
+        self.key = noise_key(self.seed, iteration)
+        self.decision = self.policy.sample_decide(obs, key=self.key, first_env=self.first_env, want_probs=want_probs,
+                                                  want_features=want_features, status=status)
+        return self.decision
+
+    def step(self, obs, t, status=None):
+        self._check(obs, "step")
+        if self.decision is None:
+            raise ValueError("SamplingSession.step before begin")
+        d = self.decision
+        r = self.policy.sample_act(obs, d.a_d, d.closest, key=self.key, first_env=self.first_env, t=t, status=status)
+        self.act, self.logp, self.feat_c = r.act, r.logp, r.feat_c
+        return r.actions

@@ -21,6 +21,7 @@ import os
 import torch
 
 from . import _lib
+from .policy import noise_key
 
 NF_C = 13
 _CTR_STEP = 1 << 40  # counter stride between time steps (global env*slot index below it)
@@ -254,7 +255,7 @@ class RolloutGPU:
     def draw_noise(self, seed, iteration):
         """Philox perf-mode noise for one iteration (global-env-id counters)."""
         L = _lib.lib()
-        key = (int(seed) * 1000003 + int(iteration)) & 0xFFFFFFFFFFFFFFFF
+        key = noise_key(seed, iteration)
         off = int(self.venv.cfg.env_id_offset)
         st = _lib.stream_ptr(device=self.venv.device)
         _lib.check(L.mhppo_philox_uniform(key, off * self.S * self.P, _lib.ptr(self.u), self.u.numel(), st))

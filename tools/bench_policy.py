@@ -6,6 +6,13 @@ HIP events around single launches after warm-up, medians of --reps with min-max,
 Observation rows: 64 envs x 70 random-action steps, repeated to M rows; the yardsticks' feature rows
 are the same rows' features (tools/hostpolicy.py), repeated alike; a_d from decide.
 Target per launch: no longer than its yardstick plus the yardstick's own min-max spread in this run.
+The stochastic launches (mhppo_policy_sample_decide / _sample_act) are timed in the same process,
+interleaved with the deterministic ones they are measured against:
+  sample_decide (feat_d NULL)  vs mhppo_policy_decide with probs;
+  sample_decide (with feat_d)  vs the same plus a device copy of M S P choice_dim floats (the bytes it adds);
+  sample_act                   vs mhppo_policy_act;
+  the in-kernel Philox forms   vs the tape forms plus the mhppo_philox_* launch they replace.
+They print their ratio to that yardstick (no target is fixed for them).
 FLOP: 2 (32 n_in + 4096 + 32 n_out) per row and forward (13 -> 1: 9 088); act is charged the forwards
 its tiles run (a head none of a tile's live, non-override triples uses is skipped).
 
@@ -49,6 +56,24 @@ def timed(fn, reps, warm=3):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def timed_interleaved(fns, reps, warm=3):
+    """{name: (median, min, max) ms} of the launches in `fns`, alternated within every repetition."""
+    for fn in fns.values():
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
+
+
 def flop(n_in, n_out):
     return 2 * (32 * n_in + 4096 + 32 * n_out)
 
@@ -64,8 +89,12 @@ def harvest(variant, nb_car, nb_ped, nb_lines, n_envs=64, steps=70, seed=20):
     return torch.cat(rows)
 
 
-def report(name, t, yard, fl):
+def report(name, t, yard, fl, ratio_only=False):
     med, lo, hi = t
+    if ratio_only:  # a yardstick given as a time in ms: print the ratio, no target
+        print(f"  {name:44s} {med * 1e3:9.1f} us (min {lo * 1e3:.1f} max {hi * 1e3:.1f})  {med / yard:.3f} of "
+              f"{yard * 1e3:.1f} us", flush=True)
+        return
     line = f"  {name:44s} {med * 1e3:9.1f} us (min {lo * 1e3:.1f} max {hi * 1e3:.1f})"
     if fl:
         line += f"  {fl / med / 1e9:6.1f} TFLOP/s = {100 * fl / (med * 1e-3) / F32_MFMA_PEAK:.1f} % of the f32-MFMA peak"
@@ -127,5 +156,62 @@ for shape, M in ((("4cars", 4, 1, 2), 2_621_440), (("scalable", 8, 2, 4), 655_36
                timed(lambda: _lib.check(L.mhppo_policy_act(cfgp, ctypes.byref(dcr), ctypes.byref(dwt), _lib.ptr(obs),
                                                            _lib.ptr(dec), M, _lib.ptr(actions), st)), a.reps),
                y_act, n_f * 32 * flop(13, 1))
+
+    # ---- the stochastic launches, alternated with their yardsticks within every repetition
+    Q_, MS = Q, M * S
+    u = torch.rand(Q_, device="cuda")
+    eps = torch.randn(MS, device="cuda")
+    lp_d = torch.empty(Q_, dtype=torch.float32, device="cuda")
+    cl = torch.empty(MS, dtype=torch.int32, device="cuda")
+    ex = torch.empty(MS, dtype=torch.uint8, device="cuda")
+    feat_d = torch.empty((Q_, dc), dtype=torch.float32, device="cuda")
+    act = torch.empty(MS, dtype=torch.float32, device="cuda")
+    lp = torch.empty(MS, dtype=torch.float32, device="cuda")
+    feat_c = torch.empty((MS, 13), dtype=torch.float32, device="cuda")
+    key = 3 * 1000003 + 1
+    nz_u, nz_e, nz_k = _lib.PolicyNoise(), _lib.PolicyNoise(), _lib.PolicyNoise()
+    nz_u.tape, nz_e.tape = u.data_ptr(), eps.data_ptr()
+    nz_k.key, nz_k.first_env, nz_k.t = key, 0, 0
+    p = _lib.ptr
+
+    def s_decide(nz, fdp):
+        return lambda: _lib.check(L.mhppo_policy_sample_decide(cfgp, ctypes.byref(dd), p(obs), M, ctypes.byref(nz),
+                                                               p(out_a), p(lp_d), p(probs), fdp, p(cl), p(ex), None, st))
+
+    def s_act(nz, fcp):
+        return lambda: _lib.check(L.mhppo_policy_sample_act(cfgp, ctypes.byref(dcr), ctypes.byref(dwt), p(obs), p(a_d),
+                                                            p(cl), M, ctypes.byref(nz), p(actions), p(act), p(lp), fcp,
+                                                            None, st))
+    s_decide(nz_u, None)()  # closest for the act launches
+    T = timed_interleaved({
+        "y_d": lambda: _lib.check(L.mhppo_policy_decide(cfgp, ctypes.byref(dd), p(obs), M, p(out_a), p(probs), st)),
+        "t_d0": s_decide(nz_u, None),
+        "y_cp": lambda: feat_d.copy_(fd),
+        "t_d1": s_decide(nz_u, p(feat_d)),
+        "y_pu": lambda: _lib.check(L.mhppo_philox_uniform(key, 0, p(u), Q_, st)),
+        "t_dk": s_decide(nz_k, p(feat_d)),
+        "y_a": lambda: _lib.check(L.mhppo_policy_act(cfgp, ctypes.byref(dcr), ctypes.byref(dwt), p(obs), p(a_d), M,
+                                                     p(actions), st)),
+        "t_a1": s_act(nz_e, p(feat_c)),
+        "t_a0": s_act(nz_e, None),
+        "y_pn": lambda: _lib.check(L.mhppo_philox_normal(key, 1 << 40, p(eps), MS, st)),
+        "t_ak": s_act(nz_k, p(feat_c)),
+    }, a.reps)
+    y_d, t_d0, y_cp, t_d1, y_pu, t_dk = (T[k] for k in ("y_d", "t_d0", "y_cp", "t_d1", "y_pu", "t_dk"))
+    y_a, t_a1, t_a0, y_pn, t_ak = (T[k] for k in ("y_a", "t_a1", "t_a0", "y_pn", "t_ak"))
+    report("yardstick: mhppo_policy_decide (a_d + probs)", y_d, None, 0)
+    report(f"yardstick: copy of {Q_} x {dc} floats", y_cp, None, 0)
+    report("yardstick: mhppo_philox_uniform", y_pu, None, 0)
+    report("sample_decide tape, feat_d NULL", t_d0, y_d[0], 0, True)
+    report("sample_decide tape, feat_d", t_d1, y_d[0] + y_cp[0], 0, True)
+    report("sample_decide Philox, feat_d  (vs tape + philox)", t_dk, t_d1[0] + y_pu[0], 0, True)
+    n_s = int(((~use_w).any(1).sum() + use_w.any(1).sum()).item())  # no override: every live triple's head runs
+    print(f"  sample_act runs {n_s} tile forwards, mhppo_policy_act {fwd}", flush=True)
+    report("yardstick: mhppo_policy_act (decided a_d)", y_a, None, 0)
+    report("yardstick: mhppo_philox_normal", y_pn, None, 0)
+    report("sample_act tape, feat_c", t_a1, y_a[0], 0, True)
+    report("sample_act tape, feat_c NULL", t_a0, y_a[0], 0, True)
+    report("sample_act Philox, feat_c  (vs tape + philox)", t_ak, t_a1[0] + y_pn[0], 0, True)
+    del u, eps, lp_d, cl, ex, feat_d, act, lp, feat_c
     del obs, f13, fd, a_d, probs, mu, actions
     torch.cuda.empty_cache()
