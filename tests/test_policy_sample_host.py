@@ -135,6 +135,43 @@ def test_in_rule_philox_noise(shape, first_env, t):
         assert bits(x[k], y[k]), k
 
 
+def test_threaded_rows_equal_serial():
+    """tools/hostpolicy.cpp's row loops on 16 threads, on 3 (uneven runs of the 1 000 rows) and on the
+    machine's default give the plain loop's bits: every output of the four rules, the status word included
+    (scalable 4/2/2: P = 2, absent cars; the Philox forms, whose noise depends on the row's flat index)."""
+    import oracle
+    hp = _hp()
+    g = np.load(os.path.join(ROOT, "tests", "golden", "rollout_scalable_422.npz"))
+    c = hp.cfg("scalable", 4, 2, 2)
+    M = 1000
+    obs = oracle.OracleBatch("scalable", M, 4, 2, 2, seed_base=int(g["seed_base"])).reset()
+    key = hp.noise_key(7, 2)
+    bad = g["w_cross"].copy()
+    bad[-1] = np.nan
+
+    def run():
+        d = hp.sample_decide(c, g["w_choice"], obs, key=key, first_env=9)
+        a, p = hp.decide(c, g["w_choice"], obs, probs=True)
+        noise = dict(key=key, first_env=9, t=3)
+        return dict(d=d, s=hp.sample_act(c, g["w_cross"], g["w_wait"], obs, d["a_d"], d["closest"], **noise),
+                    nan=hp.sample_act(c, bad, g["w_wait"], obs, d["a_d"], d["closest"], **noise),
+                    det=dict(a_d=a, probs=p, actions=hp.act(c, g["w_cross"], g["w_wait"], obs, a)))
+
+    prev = hp.set_threads(1)
+    try:
+        serial = run()
+        assert serial["d"]["status"] == 0 and serial["s"]["status"] == 0 and serial["nan"]["status"] == 2
+        assert 0 < serial["d"]["a_d"].sum() < serial["d"]["a_d"].size and (serial["d"]["exist"] == 0).any()
+        for n in (16, 3, 0):
+            hp.set_threads(n)
+            got = run()
+            for what, ref in serial.items():
+                for k, v in ref.items():
+                    assert (got[what][k] == v) if k == "status" else bits(got[what][k], v), (n, what, k)
+    finally:
+        hp.set_threads(prev)
+
+
 def test_nan_status():
     """NaN probabilities set status bit 1, a NaN loc bit 2."""
     import oracle

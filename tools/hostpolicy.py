@@ -32,6 +32,14 @@ for _name, _args in (("hp_dims", [ctypes.POINTER(EnvCfg), P]),
                      ("hp_sample_noise", [ctypes.POINTER(EnvCfg), I64, U64, U64, I64, P, P])):
     getattr(L, _name).restype = ctypes.c_int
     getattr(L, _name).argtypes = _args
+L.hp_set_threads.restype = ctypes.c_int
+L.hp_set_threads.argtypes = [ctypes.c_int]
+
+
+def set_threads(n):
+    """Threads of decide / act / sample_decide / sample_act's row loops from here on: 1 .. 16 (1: the plain
+    loop), 0: one per CPU, 16 at most (the default).  Returns the previous setting."""
+    return int(L.hp_set_threads(int(n)))
 
 
 def cfg(variant, nb_car, nb_ped, nb_lines, dt=0.3, car_b=CAR_B):
