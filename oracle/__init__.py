@@ -55,17 +55,38 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _bounds(x, shape):
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError(f"expected bounds of shape {shape}, got {a.shape}")
+    return a
+
+
+def env_kwargs(cfg):
+    """OracleEnv / OracleBatch keywords of an env-config dict (the VecCrosswalk keywords dt,
+    max_episode, simulation, car_b, ped_b, cross_b; None or {} = the defaults)."""
+    cfg = dict(cfg or {})
+    kw = {k: cfg.pop(k) for k in ("dt", "max_episode", "car_b", "ped_b", "cross_b") if k in cfg}
+    if "simulation" in cfg:
+        kw["sin"] = cfg.pop("simulation") == "sin"
+    if cfg:
+        raise TypeError(f"unknown env-config keys {sorted(cfg)}")
+    return kw
+
+
 class OracleEnv:
     """One reference env on its own CPython random stream."""
 
-    def __init__(self, variant, nb_car, nb_ped, nb_lines, dt=0.3, max_episode=80, sin=True, seed=None, flags=0):
+    def __init__(self, variant, nb_car, nb_ped, nb_lines, dt=0.3, max_episode=80, sin=True, seed=None, flags=0,
+                 car_b=CAR_B, ped_b=PED_B, cross_b=CROSS_B):
         L = lib()
         self.variant = variant
         self.nb_car, self.nb_ped, self.nb_lines = nb_car, nb_ped, nb_lines
-        self.S = 2 * nb_lines if variant == "scalable" else nb_car
-        self._cb = np.ascontiguousarray(CAR_B, dtype=np.float64)
-        self._pb = np.ascontiguousarray(PED_B, dtype=np.float64)
-        self._xb = np.ascontiguousarray(CROSS_B, dtype=np.float64)
+        self.S = 2 * nb_lines if variant == "scalable" else nb_car  # reward columns
+        self.A = 2 * nb_car if variant == "4cars2" else self.S      # action slots (4cars2: AVs and followers)
+        self._cb = _bounds(car_b, (2, 2))
+        self._pb = _bounds(ped_b, (2, 4))
+        self._xb = _bounds(cross_b, (2,))
         self.h = L.oracle_env_create(VARIANTS[variant], nb_car, nb_ped, nb_lines, dt, max_episode, int(sin),
                                      _p(self._cb), _p(self._pb), _p(self._xb))
         if not self.h:
@@ -139,7 +160,7 @@ class OracleBatch:
     (batch_oracle.c).  Same per-env code as OracleEnv."""
 
     def __init__(self, variant, n, nb_car, nb_ped, nb_lines, seed_base=0, dt=0.3, max_episode=80, sin=True,
-                 flags=0):
+                 flags=0, car_b=CAR_B, ped_b=PED_B, cross_b=CROSS_B):
         L = lib()
         P_, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
         L.oracle_batch_create.restype = P_
@@ -155,10 +176,11 @@ class OracleBatch:
         L.oracle_batch_rollout.argtypes = [P_, I, P_, P_, P_, ctypes.c_float, ctypes.c_float] + [P_] * 14
         self.variant, self.n = variant, n
         self.nb_car, self.nb_ped, self.nb_lines = nb_car, nb_ped, nb_lines
-        self.S = 2 * nb_lines if variant == "scalable" else nb_car
-        self._cb = np.ascontiguousarray(CAR_B, dtype=np.float64)
-        self._pb = np.ascontiguousarray(PED_B, dtype=np.float64)
-        self._xb = np.ascontiguousarray(CROSS_B, dtype=np.float64)
+        self.S = 2 * nb_lines if variant == "scalable" else nb_car  # reward columns
+        self.A = 2 * nb_car if variant == "4cars2" else self.S      # action slots (4cars2: AVs and followers)
+        self._cb = _bounds(car_b, (2, 2))
+        self._pb = _bounds(ped_b, (2, 4))
+        self._xb = _bounds(cross_b, (2,))
         self.h = L.oracle_batch_create(VARIANTS[variant], n, nb_car, nb_ped, nb_lines, dt, max_episode, int(sin),
                                        _p(self._cb), _p(self._pb), _p(self._xb), seed_base, int(flags))
         if not self.h:
@@ -179,7 +201,7 @@ class OracleBatch:
     def step(self, actions, want_dump=False):
         """-> obs, rewards, reward_light, done, dump (or None), mti (RNG cursor after the step)."""
         a = np.ascontiguousarray(actions, dtype=np.float64)
-        assert a.shape == (self.n, 2 * self.S)
+        assert a.shape == (self.n, 2 * self.A)
         o = np.zeros((self.n, self.obs_dim), np.float32)
         r = np.zeros((self.n, self.S), np.float64)
         rl = np.zeros((self.n, self.S), np.float64)
@@ -248,11 +270,12 @@ def choice_dim(variant, S):
 
 
 def rollout(variant, nb_car, nb_ped, nb_lines, seeds, w_cross, w_wait, w_choice, mean=-1.0, std=3.0,
-            forced_a=None, u=None, eps=None, T=80):
+            forced_a=None, u=None, eps=None, T=80, env_cfg=None):
     """One oracle episode per seed (Env_rollout.iterations_rand semantics).
 
     w_*: packed float32 weights (Model_PPO.packed()); forced_a int32 [N,S,P] or u float32 [N,S,P];
-    eps float32 [T,N,S].  Returns dict of numpy arrays laid out like the GPU buffers."""
+    eps float32 [T,N,S]; env_cfg: the env's configuration (env_kwargs), None = the defaults.
+    Returns dict of numpy arrays laid out like the GPU buffers."""
     L = lib()
     P_ = ctypes.c_void_p
     L.oracle_rollout_episode.restype = ctypes.c_int
@@ -269,8 +292,9 @@ def rollout(variant, nb_car, nb_ped, nb_lines, seeds, w_cross, w_wait, w_choice,
                ep_min=np.zeros((N, S), np.float64))
     wc, ww, wd = (np.ascontiguousarray(w, np.float32) for w in (w_cross, w_wait, w_choice))
     eps = np.ascontiguousarray(eps, np.float32)
+    kw = env_kwargs(env_cfg)
     for n, sd in enumerate(seeds):
-        env = OracleEnv(variant, nb_car, nb_ped, nb_lines, seed=int(sd))
+        env = OracleEnv(variant, nb_car, nb_ped, nb_lines, seed=int(sd), **kw)
         fa = None if forced_a is None else np.ascontiguousarray(forced_a[n], np.int32)
         uu = np.ascontiguousarray(u[n] if u is not None else np.zeros((S, nb_ped)), np.float32)
         ep = np.ascontiguousarray(eps[:, n, :], np.float32)
@@ -285,13 +309,23 @@ def rollout(variant, nb_car, nb_ped, nb_lines, seeds, w_cross, w_wait, w_choice,
 
 
 def evaluate(variant, nb_car, nb_ped, nb_lines, seeds, episodes, w_cross, w_wait, w_choice, mean=-1.0, std=3.0,
-             acc_lo=-4.0, acc_hi=2.0, dt=0.3, T=80, choix=False):
+             acc_lo=None, acc_hi=None, dt=None, T=80, choix=False, env_cfg=None, resets=1):
     """Algo_PPO.evaluate (:738-747) restated: Env_rollout.reset() — which resets the env,
     consuming that reset's draws (:125-129) — then Env_rollout.iterations (deterministic
     evaluation): for each seed, `episodes` consecutive episodes on one env.  Returns a list (one per seed) of dicts shaped like
     the five tensors iterations returns: obs [K*T, obs_dim], acts [K*T, S], rews_c
-    [K*T, S], rews_d [saves, S], waiting [saves * P]."""
+    [K*T, S], rews_d [saves, S], waiting [saves * P].
+
+    env_cfg: the env's configuration (env_kwargs), None = the defaults; the policy's acceleration
+    clamp acc_lo / acc_hi (car_b[0,0] / car_b[1,0]) and its dt follow from it unless given.
+    resets: env resets before the episodes (1: Env_rollout.reset(); 2: Env_rollout's constructor resets
+    the env too (:107), as when Algo_PPO is built on a fresh env and evaluates at once)."""
     L = lib()
+    kw = env_kwargs(env_cfg)
+    cb = _bounds(kw.get("car_b", CAR_B), (2, 2))
+    acc_lo = float(cb[0, 0]) if acc_lo is None else acc_lo
+    acc_hi = float(cb[1, 0]) if acc_hi is None else acc_hi
+    dt = float(kw.get("dt", 0.3)) if dt is None else dt
     P_ = ctypes.c_void_p
     L.oracle_eval_episode.restype = ctypes.c_int
     L.oracle_eval_episode.argtypes = [P_, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P_, P_, P_,
@@ -301,9 +335,10 @@ def evaluate(variant, nb_car, nb_ped, nb_lines, seeds, episodes, w_cross, w_wait
     wc, ww, wd = (np.ascontiguousarray(w, np.float32) for w in (w_cross, w_wait, w_choice))
     res = []
     for sd in seeds:
-        env = OracleEnv(variant, nb_car, nb_ped, nb_lines, seed=int(sd))
+        env = OracleEnv(variant, nb_car, nb_ped, nb_lines, seed=int(sd), **kw)
         od = env.obs_dim
-        env.reset()  # Env_rollout.reset()
+        for _ in range(resets):
+            env.reset()  # Env_rollout.reset()
         acc = {k: [] for k in ("obs", "acts", "rews_c", "rews_d", "waiting")}
         for _ in range(episodes):
             o = dict(obs=np.zeros((T, od), np.float32), acts=np.zeros((T, S), np.float32),

@@ -35,7 +35,7 @@ int oracle_rollout_episode(OEnv *e, int variant, int S, int P, int T, const floa
                            float *o_logp, double *o_rew, double *o_ep_min);
 
 typedef struct OBatch {
-    int n, variant, S, P, rs, od, dk;
+    int n, variant, S, A, P, rs, od, dk;
     OEnv **e;
 } OBatch;
 
@@ -44,7 +44,8 @@ int oracle_set_threads(int n) {
     return omp_get_max_threads();
 }
 
-/* rs = reward width of one env (S; 4cars2: nb_car); dk = oracle_env_dump width. */
+/* rs = reward width of one env (S; 4cars2: nb_car); A = its action slots (S; 4cars2: the AVs
+ * and the PPO-driven followers, 2 * nb_car); dk = oracle_env_dump width. */
 OBatch *oracle_batch_create(int variant, int n, int nb_car, int nb_ped, int nb_lines, double dt, int max_episode,
                             int sin_model, const double *car_b, const double *ped_b, const double *cross_b,
                             uint64_t seed_base, int flags) {
@@ -74,6 +75,7 @@ OBatch *oracle_batch_create(int variant, int n, int nb_car, int nb_ped, int nb_l
     }
     b->S = variant == 2 ? 2 * nb_lines : nb_car;
     b->rs = b->S;
+    b->A = variant == 4 ? 2 * nb_car : b->S;
     b->od = oracle_env_obs_dim(b->e[0]);
     double tmp[4096];
     b->dk = oracle_env_dump(b->e[0], tmp);
@@ -95,13 +97,13 @@ void oracle_batch_reset(OBatch *b, float *obs) {
     for (int i = 0; i < b->n; i++) oracle_env_reset(b->e[i], obs + (size_t)i * b->od);
 }
 
-/* actions float64 [n, 2S]; obs f32 [n, od]; rew / rl f64 [n, rs]; done u8 [n];
+/* actions float64 [n, 2A]; obs f32 [n, od]; rew / rl f64 [n, rs]; done u8 [n];
  * dump f64 [n, dk] and mti i32 [n] nullable (state after the step). */
 void oracle_batch_step(OBatch *b, const double *actions, float *obs, double *rew, double *rl, uint8_t *done,
                        double *dump, int32_t *mti) {
 #pragma omp parallel for schedule(static)
     for (int i = 0; i < b->n; i++) {
-        done[i] = (uint8_t)oracle_env_step(b->e[i], actions + (size_t)i * 2 * b->S, obs + (size_t)i * b->od,
+        done[i] = (uint8_t)oracle_env_step(b->e[i], actions + (size_t)i * 2 * b->A, obs + (size_t)i * b->od,
                                            rew + (size_t)i * b->rs, rl + (size_t)i * b->rs);
         if (dump) oracle_env_dump(b->e[i], dump + (size_t)i * b->dk);
         if (mti) {

@@ -5,7 +5,8 @@ one reset, then T steps of forced actions.  Actions are float32 values promoted
 to float64 exactly as the reference rollout passes them (Coop-MH-PPO-scalable.py
 :454-460).  Light policies per env: constant per episode (what the reference
 rollout does), random per step, and zeros, so every detection branch runs.
-Run:  python3 tests/golden/gen/make_env_golden.py
+Run:  python3 tests/golden/gen/make_env_golden.py        (env_<name>.npz, the default configuration)
+      python3 tests/golden/gen/make_env_golden.py cfg    (envcfg_<name>_<A|B|C|D>.npz, CONFIGS below)
 """
 import contextlib
 import io
@@ -36,6 +37,29 @@ CASES = {
 }
 
 
+# Non-default env configurations (tests/test_env_config.py, tests/test_env_config_gpu.py).
+# B2: bounds whose -2 * car_b[0][0] = 6 is no power of two (the env's braking distance then divides).
+B2 = dict(car_b=[[-3.0, 8.], [1.5, 8.]], ped_b=[[-0.1, 0.5, 0.0, -4.0], [0.1, 2.0, 3., -0.25]], cross_b=[3.0, 3.5])
+CONFIGS = {
+    "A": dict(dt=0.3, max_episode=80, simulation="unif"),
+    "B": dict(dt=0.2, max_episode=50, simulation="sin"),
+    "C": dict(dt=0.3, max_episode=80, simulation="sin", **B2),
+    "D": dict(dt=0.5, max_episode=25, simulation="unif", **B2),
+}
+# name: (variant, nb_car, nb_ped, nb_lines, n_envs, seed_base, config); max_episode + 10 steps each, so
+# every env is stepped past its done
+CFG_CASES = {
+    "coop_212_C": ("coop", 2, 1, 2, 6, 1200, "C"),
+    "coop_432_B": ("coop", 4, 3, 2, 6, 1250, "B"),
+    "4cars_412_A": ("4cars", 4, 1, 2, 6, 1300, "A"),
+    "scalable_814_D": ("scalable", 8, 1, 4, 6, 1400, "D"),
+    "scalable_432_C": ("scalable", 4, 3, 2, 6, 1450, "C"),
+    "naif_111_B": ("naif", 1, 1, 1, 6, 1500, "B"),
+    "4cars2_412_D": ("4cars2", 4, 1, 2, 6, 1600, "D"),
+    "stop_222_A": ("stop", 2, 2, 2, 6, 1700, "A"),
+}
+
+
 def n_slots(variant, nb_car, nb_lines):
     """Action slots: acc + light per slot (4cars2: AVs and PPO-driven followers)."""
     if variant == "scalable":
@@ -53,12 +77,16 @@ def count_events(text):
     return [sum(1 for ln in lines if ln.startswith(m)) for m in EVENTS]
 
 
-def run_case(variant, nb_car, nb_ped, nb_lines, n_envs, seed_base, steps, capture_events=False):
+def run_case(variant, nb_car, nb_ped, nb_lines, n_envs, seed_base, steps, capture_events=False, dt=0.3,
+             max_episode=80, simulation="sin", car_b=R.CAR_B, ped_b=R.PED_B, cross_b=R.CROSS_B):
+    """Forced accelerations are uniform in [car_b[0][0] - 0.5, car_b[1][0] + 0.5] (the defaults' [-4.5, 2.5])."""
     S = n_slots(variant, nb_car, nb_lines)
+    acc_lo, acc_hi = float(np.asarray(car_b)[0][0]) - 0.5, float(np.asarray(car_b)[1][0]) + 0.5
     arng = np.random.default_rng(seed_base)
     envs, streams = [], []
     for e in range(n_envs):
-        envs.append(R.make(variant, nb_car, nb_ped, nb_lines))
+        envs.append(R.make(variant, nb_car, nb_ped, nb_lines, dt=dt, max_episode=max_episode, simulation=simulation,
+                           car_b=car_b, ped_b=ped_b, cross_b=cross_b))
         streams.append(R.Stream(seed_base + e))
     obs0, mti0, obs, rew, rl, done, mti, dumps, acts = [], [], [], [], [], [], [], [], []
     for e in range(n_envs):
@@ -72,7 +100,7 @@ def run_case(variant, nb_car, nb_ped, nb_lines, n_envs, seed_base, steps, captur
     for t in range(steps):
         o_t, r_t, l_t, d_t, m_t, x_t, a_t, ev_t = [], [], [], [], [], [], [], []
         for e in range(n_envs):
-            acc = arng.uniform(-4.5, 2.5, size=S).astype(np.float32).astype(np.float64)
+            acc = arng.uniform(acc_lo, acc_hi, size=S).astype(np.float32).astype(np.float64)
             if modes[e] == 0:
                 light = const_light[e]
             elif modes[e] == 1:
@@ -104,7 +132,35 @@ def run_case(variant, nb_car, nb_ped, nb_lines, n_envs, seed_base, steps, captur
     )
 
 
+def save_npz(path, d):
+    """np.savez_compressed with fixed member timestamps: the same data gives the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in d.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(zi, buf.getvalue())
+
+
+def main_cfg():
+    """tests/golden/envcfg_<shape>_<A|B|C|D>.npz: the env fixtures' keys, the configuration and the events."""
+    for name, (v, nc, npd, nl, n_envs, seed, cid) in CFG_CASES.items():
+        cfg = CONFIGS[cid]
+        d = run_case(v, nc, npd, nl, n_envs, seed, cfg["max_episode"] + 10, capture_events=True, **cfg)
+        d.update(dt=cfg["dt"], max_episode=cfg["max_episode"], simulation=cfg["simulation"],
+                 car_b=np.array(cfg.get("car_b", R.CAR_B), dtype=np.float64),
+                 ped_b=np.array(cfg.get("ped_b", R.PED_B), dtype=np.float64),
+                 cross_b=np.array(cfg.get("cross_b", R.CROSS_B), dtype=np.float64))
+        path = os.path.join(OUT, f"envcfg_{name}.npz")
+        save_npz(path, d)
+        print(name, d["obs"].shape, d["events"].sum(axis=(0, 1)), os.path.getsize(path))
+
+
 def main():
+    if sys.argv[1:] == ["cfg"]:  # the non-default configurations only; the env_* fixtures stay as they are
+        return main_cfg()
     for name, case in CASES.items():
         d = run_case(*case)
         path = os.path.join(OUT, f"env_{name}.npz")

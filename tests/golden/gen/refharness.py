@@ -36,9 +36,11 @@ IDS = {
 }
 
 
-def make(variant, nb_car, nb_ped, nb_lines, dt=0.3, max_episode=80, simulation="sin"):
+def make(variant, nb_car, nb_ped, nb_lines, dt=0.3, max_episode=80, simulation="sin", car_b=CAR_B, ped_b=PED_B,
+         cross_b=CROSS_B):
     with contextlib.redirect_stdout(io.StringIO()):
-        return gym.make(IDS[variant], car_b=CAR_B, ped_b=PED_B, cross_b=CROSS_B, nb_car=nb_car,
+        return gym.make(IDS[variant], car_b=np.array(car_b, dtype=np.float64), ped_b=np.array(ped_b, dtype=np.float64),
+                        cross_b=np.array(cross_b, dtype=np.float64), nb_car=nb_car,
                         nb_ped=nb_ped, nb_lines=nb_lines, dt=dt, max_episode=max_episode,
                         simulation=simulation)
 

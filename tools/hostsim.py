@@ -29,15 +29,19 @@ def _p(a):
 
 
 class HostVec:
-    def __init__(self, variant, N, nb_car, nb_ped, nb_lines, seed_base=0, flags=0):
+    def __init__(self, variant, N, nb_car, nb_ped, nb_lines, seed_base=0, flags=0, dt=0.3, max_episode=80,
+                 simulation="sin", car_b=CAR_B, ped_b=PED_B, cross_b=CROSS_B):
         c = _lib.EnvCfg()
         c.variant, c.n_envs, c.nb_car, c.nb_ped, c.nb_lines = VARIANTS[variant], N, nb_car, nb_ped, nb_lines
-        c.max_episode, c.sin_model, c.dt = 80, 1, 0.3
-        for i, v in enumerate(np.ravel(CAR_B)):
+        c.max_episode, c.sin_model, c.dt = max_episode, int(simulation == "sin"), dt
+        for b, n in ((car_b, 4), (ped_b, 8), (cross_b, 2)):
+            if np.size(b) != n:
+                raise ValueError(f"expected {n} bound values, got {np.size(b)}")
+        for i, v in enumerate(np.ravel(car_b)):
             c.car_b[i] = v
-        for i, v in enumerate(np.ravel(PED_B)):
+        for i, v in enumerate(np.ravel(ped_b)):
             c.ped_b[i] = v
-        c.cross_b[0], c.cross_b[1] = CROSS_B
+        c.cross_b[0], c.cross_b[1] = np.ravel(cross_b)
         c.seed_base = seed_base
         c.flags = flags
         self.c = c
