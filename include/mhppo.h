@@ -718,6 +718,46 @@ int mhppo_policy_sample_act(const mhppo_env_cfg *cfg, const mhppo_mlp *actor_cro
                             const mhppo_policy_noise *noise, double *actions, float *act, float *logp, float *feat_c,
                             uint32_t *status, void *stream);
 
+/* ---- external rollouts: the record pass (csrc/rollout_record.hip; opt-in, beyond the reference,
+ * whose rollout owns its env) ---- */
+
+/* The collector's bookkeeping between a sampling step and the bucketing, for M parallel streams of
+ * S slots whose observation rows and rewards come from outside the library: what
+ * mhppo_rollout_begin and mhppo_rollout_sample_env keep of an episode, without an env handle.
+ * Segment s = row * S + slot, NS = M S <= 2^31 - 1.  The calls run on the current device.
+ *
+ * begin   ep_min[s] = +0.0 for every s (float64 [M, S]).  With rec_of (int32 [NS + M + 1]; NULL: the
+ *         identity layout) the compact record layout of mhppo_rollout_bufs.rec_of, from exist (uint8
+ *         [M, S]): rec_of[s] = the number of s' < s with exist[s'] != 0 if exist[s] != 0, else -1;
+ *         rec_of[NS + r] = the number of s' < r S with exist[s'] != 0, r = 0 .. M.  Bit for bit what
+ *         mhppo_rollout_begin writes for the same exist.
+ *         work: mhppo_record_work_bytes(M, S) bytes of device scratch, 8-byte aligned, the caller's
+ *         own (needed with rec_of only): calls on different streams with different work buffers are
+ *         independent.  Two small launches and a memset; no atomics, nothing depends on the grid.
+ * step    step t < T of the episode, one launch.  In: act, logp float32 [M, S] and feat_c float32
+ *         [M, S, 13] as mhppo_policy_sample_act writes them, rew and rew_light float64 [M, S] as the
+ *         simulator's step returns them.  The time-major records obs_c_tm float32 [T, NS, 13],
+ *         act_tm, logp_tm float32 [T, NS], rew_tm float64 [T, NS]: segment s goes to record
+ *         t NS + r, r = s with rec_of NULL (every segment is stored), else r = rec_of[s] (nothing is
+ *         stored for rec_of[s] < 0).  The copies are bitwise: NaN payloads and signed zeros survive.
+ *         For EVERY segment, stored or not, with m = ep_min[s] and x = rew_light[s]:
+ *           ep_min[s] = (m != m) ? m : ((x != x) ? x : (x < m ? x : m))
+ *         (np.minimum: a NaN stays, and of +0.0 and -0.0 the old value stays).
+ *         rec_of must be one that begin (or mhppo_rollout_begin) wrote: the kernel relies on the
+ *         ranks of consecutive present segments being consecutive, and stores a block of 256
+ *         segments' records as one contiguous run per array (16-byte stores between the run's
+ *         ends; the arrays need their natural alignment only).  A block whose run would leave
+ *         [0, NS) stores no records.  No atomics, nothing depends on the grid.
+ * M == 0 launches nothing and touches nothing.
+ * MHPPO_EINVAL, nothing written: M < 0, S < 1, M S > 2^31 - 1; begin: for M > 0 a NULL ep_min, or
+ * rec_of without exist or work; step: t outside [0, T), for M > 0 a NULL pointer other than rec_of. */
+int64_t mhppo_record_work_bytes(int64_t M, int32_t S);
+int mhppo_record_begin(const uint8_t *exist, int64_t M, int32_t S, int32_t *rec_of, double *ep_min, void *work,
+                       void *stream);
+int mhppo_record_step(int64_t M, int32_t S, int32_t t, int32_t T, const float *act, const float *logp,
+                      const float *feat_c, const double *rew, const double *rew_light, const int32_t *rec_of,
+                      float *obs_c_tm, float *act_tm, float *logp_tm, double *rew_tm, double *ep_min, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

@@ -6,5 +6,6 @@ the reference's Gym env / Model_PPO / Env_rollout / Algo_PPO surface on top.
 """
 from .env import VecCrosswalk  # noqa: F401
 from .policy import Policy, PolicySession, SamplingSession  # noqa: F401
+from .external import ExternalRollout  # noqa: F401
 
 __version__ = "0.1.0"

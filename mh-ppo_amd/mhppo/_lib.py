@@ -130,6 +130,9 @@ _SIGS = {
                                          ctypes.POINTER(PolicyNoise)] + [P] * 8),
     "mhppo_policy_sample_act": (I32, [ctypes.POINTER(EnvCfg), ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, I64,
                                       ctypes.POINTER(PolicyNoise)] + [P] * 6),
+    "mhppo_record_work_bytes": (I64, [I64, I32]),
+    "mhppo_record_begin": (I32, [P, I64, I32, P, P, P, P]),
+    "mhppo_record_step": (I32, [I64, I32, I32, I32] + [P] * 12),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }

@@ -224,6 +224,7 @@ class Algo_PPO:
         self.grad_norms = []
         self._pending_norms = []  # (pinned [10, 2H] norms, event, iteration, head names)
         self._norms_dev = None    # update()'s (norms tensor, head names) of the current iteration
+        self._external = None     # train_external's ((M, T), ExternalRollout): its buffers are allocated once
 
     def nets(self):
         return [self.actor_net_cross, self.actor_net_wait, self.actor_net_choice, self.critic_net_cross,
@@ -435,36 +436,77 @@ class Algo_PPO:
             self.rollout.iterations_rand(self.actor_net_cross, self.actor_net_wait, self.actor_net_choice,
                                          self.cov_mat, self.cov_mat_d, self.batch_size, forced_choice=fc,
                                          eps_tape=et)
-            m_c, m_w, m_d = self.update()
-            dev = self.venv.device
-            diag = getattr(self, "_diag_on", False)
-            if diag and self.total_loop % max(1, int(self.diagnostics_every)) == 0:
-                self._queue_diagnostics()
-            if getattr(self, "_norms_dev", None) is not None:
-                self._queue_grad_norms()
-            # the reward curves' sums over (cross, wait, choice): from the bucketing pass on the GPU
-            # (bucket_segments: fixed-order float64 partials), else torch reductions
-            sums = (self.rollout.choice or {}).get("rew_sums")
-            if sums is None:
-                rc, rw, rd = self.rollout.immediate_rewards()
-                sums = torch.stack([rc.double().sum(), rw.double().sum(), rd.double().sum()]).to(dev)
-            elif ppo._dp():
-                sums = sums.clone()  # the all-reduce below is in place
-            ppo._allreduce_(sums)
-            # the reward curves take the sums without a host sync here
-            self._pending_curves.append(_readback(sums, m_c, m_w, m_d))
-            if self.verbose:
-                self._flush_curves()
-            if self.verbose and _rank() == 0:
-                print("Episode * {} * And Number of steps is ==> {}".format(ep, ep * self.batch_size))
-                print("Average Cross reward is ==> {}, Average Wait reward is ==> {}".format(
-                    np.mean(self.ep_reward_cross[-10:]) if self.ep_reward_cross else float("nan"),
-                    np.mean(self.ep_reward_wait[-10:]) if self.ep_reward_wait else float("nan")))
-                print("Average Choice reward is ==> {}".format(np.mean(self.ep_reward_choice[-10:])))
-                print("Number Cross is ==> {} and Number Wait is ==> {} ".format(int(m_c), int(m_w)))
+            self._after_collect(ep)
+        self._finish_train()
+
+    def train_external(self, sim, nb_loop, M, T=None):
+        """train() with the rollout replaced (opt-in, beyond the reference): every iteration plays one
+        episode of M parallel streams in `sim` -- anything with reset() -> obs float32 [M, obs_dim] and
+        step(actions float64 [M, 2S]) -> (obs, rew, rew_light, ...) on this algo's device -- through
+        mhppo.external.ExternalRollout on self.policy(), with the collector's noise of (rollout.seed,
+        rollout.iteration) and the env's env_id_offset as the first global env id; then the bucketing
+        and everything train() does from update() on.  The algo's own env is the config carrier only
+        (it may have n_envs = 1) and is not touched: no rollout.reset().  Episodes have the fixed length
+        T (default: the env's max_episode); a simulator that ends one early keeps emitting rows and
+        rewards up to T.  Under data parallelism every rank feeds its own simulator shard."""
+        from .external import ExternalRollout
+        r = self.rollout
+        r.fix_bucket = self.fix_bucket
+        lam = getattr(self, "gae_lambda", None)
+        r.gae = None if lam is None else (self.critic_net_cross, self.critic_net_wait, self.gamma, lam)
+        key = (int(M), int(T or self.max_steps))
+        if getattr(self, "_external", None) is None or self._external[0] != key:
+            self._external = (key, ExternalRollout(self.policy(), key[0], T=key[1]))
+        ext = self._external[1]
+        ext.session.first_env = int(self.venv.cfg.env_id_offset)
+        for ep in range(nb_loop):
+            ext.session.seed = int(r.seed)
+            r.batch = ext.collect(sim, r.iteration)
+            r.iteration += 1
+            r.cross, r.wait, r.choice = bucket_segments(r.batch, fix_bucket=r.fix_bucket, status=ext.status,
+                                                        gae=r.gae)
+            self._after_collect(ep, reset_env=False)
+        self._finish_train()
+
+    def _after_collect(self, ep, reset_env=True):
+        """The rest of an iteration once rollout.cross / wait / choice hold its batch: the update, the
+        queued diagnostics, gradient norms and reward-curve read-back, the closing rollout.reset()
+        (train(); train_external leaves the algo's own env alone), total_loop, and landing the previous
+        iteration's entries."""
+        m_c, m_w, m_d = self.update()
+        dev = self.venv.device
+        diag = getattr(self, "_diag_on", False)
+        if diag and self.total_loop % max(1, int(self.diagnostics_every)) == 0:
+            self._queue_diagnostics()
+        if getattr(self, "_norms_dev", None) is not None:
+            self._queue_grad_norms()
+        # the reward curves' sums over (cross, wait, choice): from the bucketing pass on the GPU
+        # (bucket_segments: fixed-order float64 partials), else torch reductions
+        sums = (self.rollout.choice or {}).get("rew_sums")
+        if sums is None:
+            rc, rw, rd = self.rollout.immediate_rewards()
+            sums = torch.stack([rc.double().sum(), rw.double().sum(), rd.double().sum()]).to(dev)
+        elif ppo._dp():
+            sums = sums.clone()  # the all-reduce below is in place
+        ppo._allreduce_(sums)
+        # the reward curves take the sums without a host sync here
+        self._pending_curves.append(_readback(sums, m_c, m_w, m_d))
+        if self.verbose:
+            self._flush_curves()
+        if self.verbose and _rank() == 0:
+            print("Episode * {} * And Number of steps is ==> {}".format(ep, ep * self.batch_size))
+            print("Average Cross reward is ==> {}, Average Wait reward is ==> {}".format(
+                np.mean(self.ep_reward_cross[-10:]) if self.ep_reward_cross else float("nan"),
+                np.mean(self.ep_reward_wait[-10:]) if self.ep_reward_wait else float("nan")))
+            print("Average Choice reward is ==> {}".format(np.mean(self.ep_reward_choice[-10:])))
+            print("Number Cross is ==> {} and Number Wait is ==> {} ".format(int(m_c), int(m_w)))
+        if reset_env:
             self.rollout.reset()
-            self.total_loop = self.total_loop + 1
-            self._land_pending(keep_last=True)  # the previous iteration's copies landed long ago
+        self.total_loop = self.total_loop + 1
+        self._land_pending(keep_last=True)  # the previous iteration's copies landed long ago
+
+    def _finish_train(self):
+        """The end of train(): every pending entry lands, rank 0 saves the reward curves (:908-916)."""
         self._land_pending()
         if _rank() == 0 and self.save_curves:
             self.save_reward_curves()

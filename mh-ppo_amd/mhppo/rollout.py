@@ -379,6 +379,12 @@ def returns_scan_tm(rew_tm, gamma=0.99):
     T = rew_tm.shape[0]
     r = rew_tm.reshape(T, -1).contiguous()
     out = torch.empty(r.shape, dtype=torch.float32, device=rew_tm.device)
+    if rew_tm.device.type != "cuda":  # the torch path's CPU form: G_t = r_t + gamma G_{t+1} in float64
+        g = torch.zeros_like(r[0])
+        for t in range(T - 1, -1, -1):
+            g = r[t] + gamma * g
+            out[t] = g.float()
+        return out.reshape(rew_tm.shape)
     with torch.cuda.device(rew_tm.device):  # the records' device and its current stream
         _lib.check(_lib.lib().mhppo_returns_scan_tm(_lib.ptr(r), _lib.ptr(out), r.shape[1], T, gamma,
                                                     _lib.stream_ptr(device=rew_tm.device)))
@@ -686,6 +692,23 @@ def scatter_positions(pos, bucket, sizes, NS, T, obs_tm, act_tm, logp_tm, ret_tm
     """scatter_buckets with the segments given as positions: segment s goes to row block pos[s]
     of bucket bucket[s] (pos < 0: no bucket); sizes = the two buckets' segment counts."""
     dev = obs_tm.device
+    if dev.type != "cuda":  # the torch path's CPU form: the same rows by index ops
+        outs = []
+        seg_all = torch.nonzero(pos >= 0).squeeze(1)
+        for b, n in enumerate(sizes):
+            seg = seg_all[bucket[seg_all] == b]
+            rows = (pos[seg].long()[:, None] * T + torch.arange(T)[None, :]).reshape(-1)
+            o = {}
+            for k, x, dt in (("obs", obs_tm, torch.float32), ("act", act_tm, torch.float32),
+                             ("logp", logp_tm, torch.float32), ("ret", ret_tm, torch.float32),
+                             ("rew", rew_tm, torch.float64)):
+                x = x.reshape(T, NS, -1)
+                buf = torch.zeros((n * T, x.shape[2]), dtype=dt)
+                buf[rows] = x[:, seg].transpose(0, 1).reshape(-1, x.shape[2])
+                o[k] = buf if k == "obs" else buf[:, 0]
+            o["n_seg"] = n
+            outs.append(o)
+        return outs
     outs, dst = [], (_lib.BucketDst * 2)()  # one size: bucket 1 unused (every bucket[s] = 0)
     for b, n in enumerate(sizes):
         o = dict(obs=torch.empty(n * T, NF_C, dtype=torch.float32, device=dev),
