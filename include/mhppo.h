@@ -758,6 +758,74 @@ int mhppo_record_step(int64_t M, int32_t S, int32_t t, int32_t T, const float *a
                       const float *feat_c, const double *rew, const double *rew_light, const int32_t *rec_of,
                       float *obs_c_tm, float *act_tm, float *logp_tm, double *rew_tm, double *ep_min, void *stream);
 
+/* ---- early episode ends of external rollouts (opt-in: ExternalRollout(early_end=True); the calls
+ * above keep their launches and their bits) ----
+ * done is per stream: uint8 [M], what a vectorised simulator's step returns.  If stream r first reports
+ * done at step t, step t is its last and its length is L_r = t + 1; done is terminal exactly as the time
+ * limit is (V = 0 after it, no bootstrap); a done raised again later is ignored.  len int32 [M]: 0 =
+ * still running (the caller memsets it to 0 when an episode begins), else L_r.  After k recorded steps
+ * the effective length of stream r is len[r] ? len[r] : k.  All row offsets are int64. */
+
+/* mhppo_record_step with done: the step's records are stored exactly as mhppo_record_step stores them,
+ * for EVERY segment, finished or not (a block's records stay one contiguous run; the ragged calls
+ * below never read a record at or past its stream's length).  ep_min[s] is updated only for segments
+ * whose stream was running on entry; len[r] = t + 1 for streams that were running on entry and have
+ * done[r] != 0.  Running on entry to step t: len[r] == 0 or len[r] == t + 1 -- steps are recorded once
+ * each, in order from 0, so t + 1 can only be this very call's write (a stream's segments can sit in
+ * two blocks).  One launch, no atomics.  MHPPO_EINVAL: as mhppo_record_step, or done / len NULL for
+ * M > 0. */
+int mhppo_record_step_done(int64_t M, int32_t S, int32_t t, int32_t T, const float *act, const float *logp,
+                           const float *feat_c, const double *rew, const double *rew_light, const int32_t *rec_of,
+                           float *obs_c_tm, float *act_tm, float *logp_tm, double *rew_tm, double *ep_min,
+                           const uint8_t *done, int32_t *len, void *stream);
+
+/* The ragged plan: the buckets' rows when every stream has its own length.  In: pos int64 [NS] / bucket
+ * int8 [NS] per record column b < NS = M S as mhppo_bucket_plan writes them, rec_of int32 [NS] or NULL
+ * (the layout the records were stored in), len int32 [M], k >= 1 the number of recorded steps (a len
+ * outside [1, k] counts as k).
+ * Out: len_rec int32 [NS] = the effective length of the stream that column b's record belongs to (the
+ * stream b / S in the identity layout, the stream of the segment s with rec_of[s] == b in the compact
+ * one), 0 for a column that holds no record.  row0 int64 [NS] = the first row of column b's segment in
+ * the shared buffer: for a used column (pos[b] >= 0) of bucket 0 the sum of len_rec[b'] over the used
+ * bucket-0 columns b' < b; of bucket 1, W0 plus the same sum over bucket-1 columns, W0 = (rows_cross +
+ * 3) / 4 * 4 (the wait bucket's 52-byte observation rows start 16-byte aligned); -1 where pos[b] < 0.
+ * A segment's rows are contiguous, row0 .. row0 + len_rec - 1; rows_cross + 3 + rows_wait <= NS k + 3.
+ * info int64 [2] (device) = {rows_cross, rows_wait}.
+ * The rows follow column order; that is the order of pos because mhppo_bucket_plan ranks a bucket's
+ * columns in column order, and (compact layout) because rec_of ascends with the segment index.
+ * Three launches (per-block sums, a one-block scan, placement): no block waits on another, no
+ * atomics.  work: mhppo_ragged_work_bytes(NS) bytes of device scratch, 8-byte aligned.
+ * MHPPO_EINVAL: M < 0, S < 1, M S > 2^31 - 1, k < 1, info or work NULL, for M > 0 a NULL pointer other
+ * than rec_of. */
+int64_t mhppo_ragged_work_bytes(int64_t NS);
+int mhppo_ragged_plan(const int64_t *pos, const int8_t *bucket, const int32_t *rec_of, const int32_t *len, int64_t M,
+                      int32_t S, int32_t k, int64_t *row0, int32_t *len_rec, int64_t *info, void *work, void *stream);
+
+/* mhppo_returns_scan_tm with a length per column: column b scans t = len_rec[b] - 1 .. 0 from G = 0 and
+ * ret[t][b] = 0 for t >= len_rec[b] (len_rec clamped to [0, T]).  len_rec == NULL: mhppo_returns_scan_tm's
+ * bits. */
+int mhppo_returns_scan_tm_len(const double *rew, float *ret, int64_t B, int32_t T, double gamma,
+                              const int32_t *len_rec, void *stream);
+
+/* mhppo_gae_tm with a length per record: record b is used at step t iff pos[b] >= 0 (or pos == NULL) and
+ * t < len_rec[b] (clamped to [0, T]); its recurrence starts from A = nv = 0 at t = len_rec[b] - 1; ret and
+ * value are 0 at and beyond the length.  V_t stays bit for bit mhppo_mlp_forward's.  len_rec == NULL:
+ * mhppo_gae_tm's bits.  Errors as mhppo_gae_tm. */
+int mhppo_gae_tm_len(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm, const double *rew_tm,
+                     const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T, double gamma, double lambda,
+                     float *ret_tm, float *value_tm, const int32_t *len_rec, void *stream);
+
+/* mhppo_bucket_scatter_sums over ragged segments: record (t, b) with row0[b] >= 0 and t < len_rec[b]
+ * (t < T) goes to row row0[b] + t of dst[bucket[b]]; nothing else is written.  rew_sums[bucket[b]] adds
+ * (double)(float)rew over exactly those records, per-block partials folded in the fixed order of
+ * mhppo_bucket_scatter_sums.  row0 / len_rec as mhppo_ragged_plan writes them; the caller's buffers
+ * hold every row row0[b] + len_rec[b] - 1.  work: mhppo_bucket_work_bytes(NS, T) bytes.
+ * MHPPO_EINVAL: NS < 0, T <= 0, dst NULL, for NS > 0 any NULL pointer. */
+int mhppo_bucket_scatter_ragged(const int64_t *row0, const int8_t *bucket, const int32_t *len_rec, int64_t NS,
+                                int32_t T, const float *obs_tm, const float *act_tm, const float *logp_tm,
+                                const float *ret_tm, const double *rew_tm, const mhppo_bucket_dst *dst,
+                                double *rew_sums, void *work, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

@@ -20,6 +20,11 @@
 // column j (tile row j) of every layer is a sum over products with input column j alone, and the
 // permlane swap of the last layer exchanges the two halves of the SAME column.  An unused record's
 // own V is discarded and its outputs are written as 0.
+//
+// k_gae_tm<true> (mhppo_gae_tm_len): record b has len_rec[b] steps (clamped to [0, T]).  That is a
+// per-lane mask on `used` where the recurrence runs: at t >= len the record writes 0 and leaves
+// A = nv = 0, so its scan starts from there at t = len - 1 (the early end is terminal).  The wave
+// still walks all T steps; V_t is untouched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,11 +57,12 @@ __device__ __forceinline__ void wave_sync() {
 
 // LDS: [critic0 image][critic1 image, if W1][2 GW input tiles]
 // split (needs W1): unit u is tile u >> 1 with critic u & 1 alone; else unit u is tile u with both
+template <bool LEN>
 __global__ void __launch_bounds__(64 * GW)
     k_gae_tm(const float *__restrict__ W0, const float *__restrict__ W1, int n_in, const float *__restrict__ obs_tm,
              const double *__restrict__ rew_tm, const int64_t *__restrict__ pos, const int8_t *__restrict__ bucket,
              int64_t B, int T, double gamma, double lambda, int split, float *__restrict__ ret_tm,
-             float *__restrict__ value_tm) {
+             float *__restrict__ value_tm, const int32_t *__restrict__ len_rec) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x, l = tid & 63, j = l & 31, kh = l >> 5, w = tid >> 6;
   const Img g = img_layout(n_in, 1);
@@ -84,6 +90,8 @@ __global__ void __launch_bounds__(64 * GW)
     }
     // the wave's records: all of the tile, or those of its critic (unused ones go with critic 0);
     // mine: the lane that owns record r's scan and outputs
+    int Lr = T;  // the record's steps
+    if (LEN && j < nr) Lr = min(max(len_rec[r], 0), T);
     const bool own = only < 0 || (used ? (int)b1 == only : only == 0);
     const bool mine = kh == 0 && j < nr && own;
     const bool any0 = only != 1 && __builtin_amdgcn_ballot_w64(used && !b1) != 0,
@@ -129,7 +137,7 @@ __global__ void __launch_bounds__(64 * GW)
       if (t > 0) stage_x_land(xn, g, xst, pre, src, nr, n_in, l);
       if (mine) {
         float ret = 0.0f;
-        if (used) {
+        if (used && (!LEN || t < Lr)) {
           const double v = (double)vf;
           const double d = (rw + gamma * nv) - v;
           A = d + c * A;
@@ -159,27 +167,28 @@ int check_critic(const mhppo_mlp *m, const char *what) {
   return MHPPO_OK;
 }
 
-LdsLimit g_lds_limit;  // k_gae_tm's dynamic LDS above the default 64 KB (wide critics)
+LdsLimit g_lds_limit[2];  // k_gae_tm<false / true>'s dynamic LDS above the default 64 KB (wide critics)
 
 int launch(const float *W0, const float *W1, int n_in, const float *obs_tm, const double *rew_tm, const int64_t *pos,
            const int8_t *bucket, int64_t B, int T, double gamma, double lambda, float *ret_tm, float *value_tm,
-           hipStream_t s) {
+           const int32_t *len_rec, hipStream_t s) {
   const Img g = img_layout(n_in, 1);
   const size_t shm = ((size_t)(W1 ? 2 : 1) * g.size + (size_t)2 * GW * xtile_floats(g)) * sizeof(float);
-  if (int rc = allow_dynamic_lds(reinterpret_cast<const void *>(k_gae_tm), shm, g_lds_limit)) return rc;
+  const auto kern = len_rec ? k_gae_tm<true> : k_gae_tm<false>;
+  if (int rc = allow_dynamic_lds(reinterpret_cast<const void *>(kern), shm, g_lds_limit[len_rec ? 1 : 0])) return rc;
   const int split = W1 && n_tiles(B) <= SPLIT_TILES;
   const int64_t units = split ? 2 * n_tiles(B) : n_tiles(B);
   const int nb = (int)std::min<int64_t>((units + GW - 1) / GW, MAX_BLOCKS);
-  hipLaunchKernelGGL(k_gae_tm, dim3((unsigned)nb), dim3(64 * GW), shm, s, W0, W1, n_in, obs_tm, rew_tm, pos, bucket,
-                     B, T, gamma, lambda, split, ret_tm, value_tm);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64 * GW), shm, s, W0, W1, n_in, obs_tm, rew_tm, pos, bucket, B, T,
+                     gamma, lambda, split, ret_tm, value_tm, len_rec);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }
-}  // namespace
 
-extern "C" int mhppo_gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm,
-                            const double *rew_tm, const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T,
-                            double gamma, double lambda, float *ret_tm, float *value_tm, void *stream) {
+// both entry points: len_rec == NULL is mhppo_gae_tm
+int gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm, const double *rew_tm,
+           const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T, double gamma, double lambda, float *ret_tm,
+           float *value_tm, const int32_t *len_rec, void *stream) {
   if (int rc = check_critic(critic0, "critic0")) return rc;
   if (pos || critic1) {
     if (int rc = check_critic(critic1, "critic1")) return rc;
@@ -196,5 +205,20 @@ extern "C" int mhppo_gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, 
   if (!obs_tm || !rew_tm || !ret_tm) return set_error(MHPPO_EINVAL, "mhppo_gae_tm: null pointer");
   const float *W0 = critic0->packed, *W1 = pos ? critic1->packed : nullptr;  // pos == NULL: critic0 alone
   const int n_in = critic0->n_in;
-  return launch(W0, W1, n_in, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, (hipStream_t)stream);
+  return launch(W0, W1, n_in, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, len_rec,
+                (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int mhppo_gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm,
+                            const double *rew_tm, const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T,
+                            double gamma, double lambda, float *ret_tm, float *value_tm, void *stream) {
+  return gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, nullptr, stream);
+}
+
+extern "C" int mhppo_gae_tm_len(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm,
+                                const double *rew_tm, const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T,
+                                double gamma, double lambda, float *ret_tm, float *value_tm, const int32_t *len_rec,
+                                void *stream) {
+  return gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, len_rec, stream);
 }

@@ -1,8 +1,11 @@
 // ppo_batch.hip — from a finished rollout's time-major records to the update's batches (+ C-ABI):
-//   k_returns / k_returns_tm   the reward-to-go scan (mhppo_returns_scan / _scan_tm)
+//   k_returns / k_returns_tm / k_returns_tm_len   the reward-to-go scan (mhppo_returns_scan / _scan_tm /
+//                              _scan_tm_len: a length per column)
 //   k_bucket_scatter           both segment-major buckets in one pass over the records, optionally
 //                              with their reward sums, folded by k_fold<1024, 4, add>
-//                              (mhppo_bucket_scatter / _scatter_sums)
+//                              (mhppo_bucket_scatter / _scatter_sums; RAGGED: _scatter_ragged)
+//   k_rag_count / _scan / _place    the ragged buckets' row offsets and lengths (mhppo_ragged_plan;
+//                              scratch size: mhppo_ragged_work_bytes)
 //   k_plan_count / _scan / _place   the bucket positions, the choice batch and the host's one info
 //                              record (mhppo_bucket_plan; scratch size: mhppo_bucket_work_bytes)
 // Every sum has a fixed order (block_prims.h: the fold and the ballot rank): the same call gives
@@ -47,6 +50,21 @@ __global__ void __launch_bounds__(TPB) k_returns_tm(const double *rew, float *re
   }
 }
 
+// the same scan of a column cut at len_rec[b] steps (clamped to [0, T]; NULL: T): G starts from 0 at
+// t = len - 1 (the early end is terminal, as the time limit is) and ret is 0 from there on
+__global__ void __launch_bounds__(TPB)
+    k_returns_tm_len(const double *rew, float *ret, int64_t B, int T, double gamma, const int32_t *len_rec) {
+  int64_t b = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (b >= B) return;
+  const int L = len_rec ? min(max(len_rec[b], 0), T) : T;
+  for (int t = T - 1; t >= L; t--) ret[(int64_t)t * B + b] = 0.0f;
+  double g = 0.0;
+  for (int t = L - 1; t >= 0; t--) {
+    g = rew[(int64_t)t * B + b] + gamma * g;
+    ret[(int64_t)t * B + b] = (float)g;
+  }
+}
+
 // ------------------------------------------------------------ bucket scatter
 // Segment-major buckets (bucket_segments; the reference's per-episode concatenation,
 // Coop-MH-PPO-scalable.py:489-507), both buckets in one pass over the time-major records:
@@ -68,13 +86,18 @@ constexpr int BTPB = MHPPO_BK_TPB;
 // SUMS (mhppo_bucket_scatter_sums): partials[b * nblocks + block] = the block's sum of
 // (double)(float)rew over its records of bucket b (wave butterflies, then the waves in order: a
 // fixed order), folded by k_fold_wide.
-template <bool SUMS>
+// RAGGED (mhppo_bucket_scatter_ragged): pos[s] is the segment's first ROW (row0) instead of its
+// position, and only its first len_rec[s] steps are records: the tile's step count is per segment,
+// ns = clamp(len_rec[s] - t0, 0, nt), its rows row0 + t0 .. + ns.  Nothing at or past a length is
+// loaded, summed or written.
+template <bool SUMS, bool RAGGED>
 __global__ void __launch_bounds__(bk::BTPB)
     k_bucket_scatter(const int64_t *__restrict__ pos, const int8_t *__restrict__ bucket, int64_t NS, int T,
                      const float *__restrict__ obs, const float *__restrict__ act, const float *__restrict__ logp,
                      const float *__restrict__ ret, const double *__restrict__ rew, mhppo_bucket_dst d0,
-                     mhppo_bucket_dst d1, double *__restrict__ partials) {
+                     mhppo_bucket_dst d1, double *__restrict__ partials, const int32_t *__restrict__ len_rec) {
   using namespace bk;
+  __shared__ int s_ns[RAGGED ? SEGS : 1];  // RAGGED: the segments' step counts in this tile
   __shared__ float s_obs[SEGS * OBS_SEG];
   __shared__ float s_v[3][SEGS * V_SEG];
   __shared__ double s_rew[SEGS * V_SEG];
@@ -88,6 +111,7 @@ __global__ void __launch_bounds__(bk::BTPB)
   if (tid < SEGS) {
     s_pos[tid] = tid < nseg ? pos[s0 + tid] : -1;
     s_b[tid] = tid < nseg ? bucket[s0 + tid] : 0;
+    if (RAGGED) s_ns[tid] = tid < nseg ? min(max(len_rec[s0 + tid] - t0, 0), nt) : 0;
   }
   __syncthreads();
   // the observation records of one step of the block's 64 segments are 64 x 13 consecutive
@@ -103,7 +127,7 @@ __global__ void __launch_bounds__(bk::BTPB)
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
       const int i = tid + q * BTPB, tl = i / (SEGS * NF_C), k = i - tl * (SEGS * NF_C), sg = k / NF_C;
-      const bool in = sg < nseg && tl < nt;
+      const bool in = sg < nseg && tl < (RAGGED ? s_ns[sg] : nt);
       at[q] = in && s_pos[sg] >= 0 ? sg * OBS_SEG + tl * NF_C + (k - sg * NF_C) : -1;
       v[q] = 0.0f;
       if (at[q] >= 0) v[q] = obs[((int64_t)(t0 + tl) * NS + s0) * NF_C + k];
@@ -116,7 +140,7 @@ __global__ void __launch_bounds__(bk::BTPB)
 #pragma unroll
   for (int i = tid; i < SEGS * STEPS; i += BTPB) {  // i = step * SEGS + seg: lanes on consecutive segments
     const int sg = i % SEGS, tl = i / SEGS;
-    if (sg >= nseg || tl >= nt || s_pos[sg] < 0) continue;
+    if (sg >= nseg || tl >= (RAGGED ? s_ns[sg] : nt) || s_pos[sg] < 0) continue;
     const int64_t rec = (int64_t)(t0 + tl) * NS + s0 + sg;
     const int o = sg * V_SEG + tl;  // LDS: segment-major
     s_v[0][o] = act[rec];
@@ -147,10 +171,11 @@ __global__ void __launch_bounds__(bk::BTPB)
     const int64_t p = s_pos[sg];
     if (p < 0) continue;
     const mhppo_bucket_dst &D = s_b[sg] ? d1 : d0;
-    const int64_t r0 = p * T + t0;
+    const int64_t r0 = RAGGED ? p + t0 : p * T + t0;
+    const int ns = RAGGED ? s_ns[sg] : nt;
     float *oo = D.obs + r0 * NF_C;
-    for (int j = l; j < nt * NF_C; j += 64) oo[j] = s_obs[sg * OBS_SEG + j];
-    if (l < nt) {
+    for (int j = l; j < ns * NF_C; j += 64) oo[j] = s_obs[sg * OBS_SEG + j];
+    if (l < ns) {
       const int o = sg * V_SEG + l;
       D.act[r0 + l] = s_v[0][o];
       D.logp[r0 + l] = s_v[1][o];
@@ -308,6 +333,123 @@ __global__ void __launch_bounds__(TPB)
   }
 }
 
+// ------------------------------------------------------------ ragged plan
+// mhppo_ragged_plan: the buckets' row offsets when the streams have lengths of their own, in the
+// bucket plan's three-launch shape (no block waits on another, no atomics): per-block sums of the
+// lengths (k_rag_count), ONE block scans them and writes info (k_rag_scan), then every block places
+// its segments by the exclusive sum of the lengths before them in the block (k_rag_place).
+// A thread owns SEGMENT s, whose record column is b = s (identity) or rec_of[s] (compact).  The sums
+// run in segment order; row0 is defined in column order.  The two agree because rec_of ascends with
+// s (mhppo_record_begin's ranks), and the rows then follow the order of pos because
+// mhppo_bucket_plan ranks the columns of a bucket in column order.
+struct RagSeg {
+  int64_t col;  // the segment's record column, -1: none
+  int len;      // the effective length of its stream
+  bool in0, in1;
+};
+__device__ inline RagSeg rag_seg(int64_t s, int64_t NS, int S, int k, const int64_t *__restrict__ pos,
+                                 const int8_t *__restrict__ bucket, const int32_t *__restrict__ rec_of,
+                                 const int32_t *__restrict__ len) {
+  RagSeg q;
+  q.col = -1, q.len = 0, q.in0 = q.in1 = false;
+  if (s >= NS) return q;
+  const int64_t b = rec_of ? (int64_t)rec_of[s] : s;
+  if (b < 0 || b >= NS) return q;
+  const int32_t L = len[s / S];
+  q.col = b;
+  q.len = (L <= 0 || L > k) ? k : L;  // 0: still running, cut at k
+  const bool used = pos[b] >= 0;
+  q.in1 = used && bucket[b] != 0;
+  q.in0 = used && !q.in1;
+  return q;
+}
+
+// v[k] <- the sum of v[k] over the threads before this one in the block, total[k] <- over all of it
+// (inclusive shuffle scan per wave, then the waves in order).  Called by every thread.
+__device__ __forceinline__ void block_excl_scan2(int64_t (&v)[2], int64_t (&total)[2]) {
+  __shared__ int64_t wsum[2][TPB / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const int64_t own = v[k];
+    int64_t x = own;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int64_t y = __shfl_up(x, d, 64);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63) wsum[k][w] = x;
+    v[k] = x - own;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    int64_t before = 0, all = 0;
+    for (int q = 0; q < TPB / 64; q++) {
+      if (q < w) before += wsum[k][q];
+      all += wsum[k][q];
+    }
+    v[k] += before;
+    total[k] = all;
+  }
+  __syncthreads();  // wsum may be written again
+}
+
+__global__ void __launch_bounds__(TPB)
+    k_rag_count(int64_t NS, int S, int k, const int64_t *__restrict__ pos, const int8_t *__restrict__ bucket,
+                const int32_t *__restrict__ rec_of, const int32_t *__restrict__ len, int nblk,
+                int64_t *__restrict__ sums, int64_t *__restrict__ row0, int32_t *__restrict__ len_rec) {
+  const int64_t s = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  const RagSeg q = rag_seg(s, NS, S, k, pos, bucket, rec_of, len);
+  if (s < NS) {  // as a COLUMN index: k_rag_place fills in the columns that hold a record
+    row0[s] = -1;
+    len_rec[s] = 0;
+  }
+  int64_t v[2] = {q.in0 ? q.len : 0, q.in1 ? q.len : 0}, total[2];
+  block_excl_scan2(v, total);
+  if (threadIdx.x == 0) {
+    sums[blockIdx.x] = total[0];
+    sums[(size_t)nblk + blockIdx.x] = total[1];
+  }
+}
+
+// one block: base[k][b] = the sum of sums[k][0 .. b) (tiles of TPB blocks, a running carry), info = the totals
+__global__ void __launch_bounds__(TPB)
+    k_rag_scan(const int64_t *__restrict__ sums, int nblk, int64_t *__restrict__ base, int64_t *__restrict__ info) {
+  int64_t carry[2] = {0, 0};
+  for (int b0 = 0; b0 < nblk; b0 += TPB) {
+    const int b = b0 + threadIdx.x;
+    int64_t v[2] = {b < nblk ? sums[b] : 0, b < nblk ? sums[(size_t)nblk + b] : 0}, total[2];
+    block_excl_scan2(v, total);
+    if (b < nblk) {
+      base[b] = carry[0] + v[0];
+      base[(size_t)nblk + b] = carry[1] + v[1];
+    }
+    carry[0] += total[0];
+    carry[1] += total[1];
+  }
+  if (threadIdx.x == 0) {
+    info[0] = carry[0];  // rows_cross
+    info[1] = carry[1];  // rows_wait
+  }
+}
+
+__global__ void __launch_bounds__(TPB)
+    k_rag_place(int64_t NS, int S, int k, const int64_t *__restrict__ pos, const int8_t *__restrict__ bucket,
+                const int32_t *__restrict__ rec_of, const int32_t *__restrict__ len, int nblk,
+                const int64_t *__restrict__ base, const int64_t *__restrict__ info, int64_t *__restrict__ row0,
+                int32_t *__restrict__ len_rec) {
+  const int64_t s = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  const RagSeg q = rag_seg(s, NS, S, k, pos, bucket, rec_of, len);
+  int64_t v[2] = {q.in0 ? q.len : 0, q.in1 ? q.len : 0}, total[2];
+  block_excl_scan2(v, total);
+  if (q.col < 0) return;
+  len_rec[q.col] = q.len;
+  // the wait rows start at the cross rows rounded up to a multiple of 4 (16-byte aligned 52-byte rows)
+  const int64_t w0 = (info[0] + 3) / 4 * 4;
+  if (q.in0) row0[q.col] = base[blockIdx.x] + v[0];
+  if (q.in1) row0[q.col] = w0 + base[(size_t)nblk + blockIdx.x] + v[1];
+}
+
 // the fold of the scatter's partials (two per block: many), added to rew_sums
 constexpr int FOLD_TPB = 1024;
 constexpr auto k_fold_wide = k_fold<FOLD_TPB, 4, true>;
@@ -342,8 +484,9 @@ int mhppo_bucket_scatter(const int64_t *pos, const int8_t *bucket, int64_t NS, i
   const int64_t nb = (NS + bk::SEGS - 1) / bk::SEGS;
   if (nb > 0x7fffffff) return set_error(MHPPO_EINVAL, "too many segments");
   dim3 g((unsigned)nb, (unsigned)((T + bk::STEPS - 1) / bk::STEPS));
-  hipLaunchKernelGGL(k_bucket_scatter<false>, g, dim3(bk::BTPB), 0, (hipStream_t)stream, pos, bucket, NS, (int)T,
-                     obs_tm, act_tm, logp_tm, ret_tm, rew_tm, dst[0], dst[1], (double *)nullptr);
+  hipLaunchKernelGGL((k_bucket_scatter<false, false>), g, dim3(bk::BTPB), 0, (hipStream_t)stream, pos, bucket, NS,
+                     (int)T, obs_tm, act_tm, logp_tm, ret_tm, rew_tm, dst[0], dst[1], (double *)nullptr,
+                     (const int32_t *)nullptr);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }
@@ -372,8 +515,8 @@ int mhppo_bucket_scatter_sums(const int64_t *pos, const int8_t *bucket, int64_t 
   dim3 g((unsigned)nb, (unsigned)((T + bk::STEPS - 1) / bk::STEPS));
   hipStream_t s = (hipStream_t)stream;
   double *part = (double *)work;
-  hipLaunchKernelGGL(k_bucket_scatter<true>, g, dim3(bk::BTPB), 0, s, pos, bucket, NS, (int)T, obs_tm, act_tm, logp_tm,
-                     ret_tm, rew_tm, dst[0], dst[1], part);
+  hipLaunchKernelGGL((k_bucket_scatter<true, false>), g, dim3(bk::BTPB), 0, s, pos, bucket, NS, (int)T, obs_tm, act_tm,
+                     logp_tm, ret_tm, rew_tm, dst[0], dst[1], part, (const int32_t *)nullptr);
   hipLaunchKernelGGL(k_fold_wide, dim3(2), dim3(FOLD_TPB), 0, s, part, (int)nblocks, rew_sums);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
@@ -404,6 +547,64 @@ int mhppo_bucket_plan(int64_t N, int32_t S, int32_t P, int32_t dc, const int32_t
     hipLaunchKernelGGL(k_plan_place, dim3(nblk), dim3(TPB), 0, s, NS, (int)S, (int)P, (int)dc, a_d, closest, exist,
                        rec_of, ep_min, feat_d, logp_d, (int)fix_bucket, nblk, base, info, pos, bucket, c_obs, c_act,
                        c_logp, c_ret);
+  CHECK_HIP(hipGetLastError());
+  return MHPPO_OK;
+}
+
+int mhppo_returns_scan_tm_len(const double *rew, float *ret, int64_t B, int32_t T, double gamma,
+                              const int32_t *len_rec, void *stream) {
+  if (!rew || !ret || B < 0 || T <= 0) return set_error(MHPPO_EINVAL, "returns_scan_tm_len: bad argument");
+  if (B == 0) return MHPPO_OK;
+  hipLaunchKernelGGL(k_returns_tm_len, grid_for(B), dim3(TPB), 0, (hipStream_t)stream, rew, ret, B, T, gamma, len_rec);
+  CHECK_HIP(hipGetLastError());
+  return MHPPO_OK;
+}
+
+// scratch of the ragged plan: the per-block length sums and their scans, int64 [2][nblk] each
+int64_t mhppo_ragged_work_bytes(int64_t NS) {
+  if (NS < 0) return 0;
+  return std::max<int64_t>(plan_blocks(NS) * 32, 8);
+}
+
+int mhppo_ragged_plan(const int64_t *pos, const int8_t *bucket, const int32_t *rec_of, const int32_t *len, int64_t M,
+                      int32_t S, int32_t k, int64_t *row0, int32_t *len_rec, int64_t *info, void *work,
+                      void *stream) {
+  if (M < 0 || S < 1 || M > INT32_MAX / (int64_t)S) return set_error(MHPPO_EINVAL, "ragged_plan: M < 0, S < 1 or M S > 2^31 - 1");
+  if (k < 1) return set_error(MHPPO_EINVAL, "ragged_plan: k < 1");
+  if (!info || !work) return set_error(MHPPO_EINVAL, "ragged_plan: info or work is NULL");
+  const int64_t NS = M * S;
+  if (NS > 0 && (!pos || !bucket || !len || !row0 || !len_rec))
+    return set_error(MHPPO_EINVAL, "ragged_plan: a NULL pointer other than rec_of");
+  const int nblk = (int)plan_blocks(NS);
+  int64_t *sums = (int64_t *)work, *base = sums + 2 * (size_t)nblk;
+  hipStream_t s = (hipStream_t)stream;
+  if (nblk > 0)
+    hipLaunchKernelGGL(k_rag_count, dim3(nblk), dim3(TPB), 0, s, NS, (int)S, (int)k, pos, bucket, rec_of, len, nblk, sums,
+                       row0, len_rec);
+  hipLaunchKernelGGL(k_rag_scan, dim3(1), dim3(TPB), 0, s, sums, nblk, base, info);
+  if (nblk > 0)
+    hipLaunchKernelGGL(k_rag_place, dim3(nblk), dim3(TPB), 0, s, NS, (int)S, (int)k, pos, bucket, rec_of, len, nblk, base,
+                       info, row0, len_rec);
+  CHECK_HIP(hipGetLastError());
+  return MHPPO_OK;
+}
+
+int mhppo_bucket_scatter_ragged(const int64_t *row0, const int8_t *bucket, const int32_t *len_rec, int64_t NS,
+                                int32_t T, const float *obs_tm, const float *act_tm, const float *logp_tm,
+                                const float *ret_tm, const double *rew_tm, const mhppo_bucket_dst *dst,
+                                double *rew_sums, void *work, void *stream) {
+  if (NS < 0 || T <= 0 || !dst) return set_error(MHPPO_EINVAL, "bucket_scatter_ragged: bad argument");
+  if (NS == 0) return MHPPO_OK;
+  if (!row0 || !bucket || !len_rec || !obs_tm || !act_tm || !logp_tm || !ret_tm || !rew_tm || !rew_sums || !work)
+    return set_error(MHPPO_EINVAL, "bucket_scatter_ragged: null pointer");
+  const int64_t nb = (NS + bk::SEGS - 1) / bk::SEGS, nblocks = scatter_blocks(NS, T);
+  if (nb > 0x7fffffff || nblocks > 0x7fffffff) return set_error(MHPPO_EINVAL, "bucket_scatter_ragged: too many segments");
+  dim3 g((unsigned)nb, (unsigned)((T + bk::STEPS - 1) / bk::STEPS));
+  hipStream_t s = (hipStream_t)stream;
+  double *part = (double *)work;
+  hipLaunchKernelGGL((k_bucket_scatter<true, true>), g, dim3(bk::BTPB), 0, s, row0, bucket, NS, (int)T, obs_tm, act_tm,
+                     logp_tm, ret_tm, rew_tm, dst[0], dst[1], part, len_rec);
+  hipLaunchKernelGGL(k_fold_wide, dim3(2), dim3(FOLD_TPB), 0, s, part, (int)nblocks, rew_sums);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }

@@ -24,6 +24,15 @@
 //      run's ends go out word by word.  float64 values travel as two words.
 // All copies move 32-bit words: NaN payloads and signed zeros survive.  No atomics; a block's
 // work depends on its index alone.
+//
+// k_record_step<true> (mhppo_record_step_done) is the same pass with early episode ends: the records
+// are stored for every segment, finished or not (the one-contiguous-run-per-block store stays; the
+// bucketing never reads a record at or past its stream's length), ep_min is updated only for the
+// segments of streams that were running on entry, and the thread of a running stream's slot 0 sets
+// len[r] = t + 1 when done[r] != 0.  The S segments of a stream can sit in two blocks, so a thread may
+// read len[r] before or after that write.  Liveness rule: a stream is running on entry to step t iff
+// len[r] == 0 or len[r] == t + 1.  Steps are recorded once each, in order, so the only value step t
+// itself can write is t + 1 and no earlier step can have written it: both reads give the same answer.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mhppo.h"
@@ -85,11 +94,13 @@ __device__ __forceinline__ void store_run(uint32_t *__restrict__ dst, const uint
   }
 }
 
+template <bool DONE>
 __global__ void __launch_bounds__(NT)
     k_record_step(int NS, int t, const uint32_t *__restrict__ act, const uint32_t *__restrict__ logp,
                   const uint32_t *__restrict__ feat, const uint2 *__restrict__ rew, const double *__restrict__ rew_light,
                   const int32_t *__restrict__ rec_of, uint32_t *__restrict__ obs_tm, uint32_t *__restrict__ act_tm,
-                  uint32_t *__restrict__ logp_tm, uint32_t *__restrict__ rew_tm, double *ep_min) {
+                  uint32_t *__restrict__ logp_tm, uint32_t *__restrict__ rew_tm, double *ep_min, int S,
+                  const uint8_t *__restrict__ done, int32_t *len) {
   // LDS images of the block's runs, each with room for its offset a <= 3 from a 16-byte boundary
   __shared__ uint4 img_o[(NT * NFC + 3 + 3) / 4];
   __shared__ uint4 img_a[(NT + 3 + 3) / 4], img_l[(NT + 3 + 3) / 4], img_r[(2 * NT + 3 + 3) / 4];
@@ -108,8 +119,17 @@ __global__ void __launch_bounds__(NT)
     va = act[s];
     vl = logp[s];
     vr = rew[s];
-    const double m = ep_min[s], x = rew_light[s];
-    ep_min[s] = (m != m) ? m : ((x != x) ? x : (x < m ? x : m));  // np.minimum: NaN-propagating
+    bool live = true;  // the segment's stream was running on entry (the header's liveness rule)
+    if (DONE) {
+      const int row = s / S;
+      const int32_t L = len[row];  // not __restrict__: slot 0's thread of this row may be writing t + 1
+      live = L == 0 || L == t + 1;
+      if (live && s == row * S && done[row] != 0) len[row] = t + 1;
+    }
+    if (live) {
+      const double m = ep_min[s], x = rew_light[s];
+      ep_min[s] = (m != m) ? m : ((x != x) ? x : (x < m ? x : m));  // np.minimum: NaN-propagating
+    }
   }
   const bool f[1] = {r >= 0};
   int before[1], total[1];
@@ -191,20 +211,42 @@ extern "C" int mhppo_record_begin(const uint8_t *exist, int64_t M, int32_t S, in
   return MHPPO_OK;
 }
 
+namespace {
+// both entry points: done == NULL is mhppo_record_step
+int record_step(const char *who, int64_t M, int32_t S, int32_t t, int32_t T, const float *act, const float *logp,
+                const float *feat_c, const double *rew, const double *rew_light, const int32_t *rec_of,
+                float *obs_c_tm, float *act_tm, float *logp_tm, double *rew_tm, double *ep_min, bool with_done,
+                const uint8_t *done, int32_t *len, void *stream) {
+  const int64_t NS = segments(M, S);
+  if (NS < 0) return set_error(MHPPO_EINVAL, "%s: M < 0, S < 1 or M S > 2^31 - 1", who);
+  if (t < 0 || t >= T) return set_error(MHPPO_EINVAL, "%s: t %d outside [0, %d)", who, t, T);
+  if (NS == 0) return MHPPO_OK;
+  if (!act || !logp || !feat_c || !rew || !rew_light || !obs_c_tm || !act_tm || !logp_tm || !rew_tm || !ep_min)
+    return set_error(MHPPO_EINVAL, "%s: a NULL source or destination", who);
+  if (with_done && (!done || !len)) return set_error(MHPPO_EINVAL, "%s: done or len is NULL", who);
+  const auto kern = with_done ? k_record_step<true> : k_record_step<false>;
+  hipLaunchKernelGGL(kern, dim3(blocks_for(NS)), dim3(NT), 0, (hipStream_t)stream, (int)NS, (int)t,
+                     (const uint32_t *)act, (const uint32_t *)logp, (const uint32_t *)feat_c, (const uint2 *)rew,
+                     rew_light, rec_of, (uint32_t *)obs_c_tm, (uint32_t *)act_tm, (uint32_t *)logp_tm,
+                     (uint32_t *)rew_tm, ep_min, (int)S, done, len);
+  CHECK_HIP(hipGetLastError());
+  return MHPPO_OK;
+}
+}  // namespace
+
 extern "C" int mhppo_record_step(int64_t M, int32_t S, int32_t t, int32_t T, const float *act, const float *logp,
                                  const float *feat_c, const double *rew, const double *rew_light,
                                  const int32_t *rec_of, float *obs_c_tm, float *act_tm, float *logp_tm,
                                  double *rew_tm, double *ep_min, void *stream) {
-  const int64_t NS = segments(M, S);
-  if (NS < 0) return set_error(MHPPO_EINVAL, "record_step: M < 0, S < 1 or M S > 2^31 - 1");
-  if (t < 0 || t >= T) return set_error(MHPPO_EINVAL, "record_step: t %d outside [0, %d)", t, T);
-  if (NS == 0) return MHPPO_OK;
-  if (!act || !logp || !feat_c || !rew || !rew_light || !obs_c_tm || !act_tm || !logp_tm || !rew_tm || !ep_min)
-    return set_error(MHPPO_EINVAL, "record_step: a NULL source or destination");
-  hipLaunchKernelGGL(k_record_step, dim3(blocks_for(NS)), dim3(NT), 0, (hipStream_t)stream, (int)NS, (int)t,
-                     (const uint32_t *)act, (const uint32_t *)logp, (const uint32_t *)feat_c, (const uint2 *)rew,
-                     rew_light, rec_of, (uint32_t *)obs_c_tm, (uint32_t *)act_tm, (uint32_t *)logp_tm,
-                     (uint32_t *)rew_tm, ep_min);
-  CHECK_HIP(hipGetLastError());
-  return MHPPO_OK;
+  return record_step("record_step", M, S, t, T, act, logp, feat_c, rew, rew_light, rec_of, obs_c_tm, act_tm, logp_tm,
+                     rew_tm, ep_min, false, nullptr, nullptr, stream);
+}
+
+extern "C" int mhppo_record_step_done(int64_t M, int32_t S, int32_t t, int32_t T, const float *act, const float *logp,
+                                      const float *feat_c, const double *rew, const double *rew_light,
+                                      const int32_t *rec_of, float *obs_c_tm, float *act_tm, float *logp_tm,
+                                      double *rew_tm, double *ep_min, const uint8_t *done, int32_t *len,
+                                      void *stream) {
+  return record_step("record_step_done", M, S, t, T, act, logp, feat_c, rew, rew_light, rec_of, obs_c_tm, act_tm,
+                     logp_tm, rew_tm, ep_min, true, done, len, stream);
 }

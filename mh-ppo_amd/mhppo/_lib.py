@@ -133,6 +133,12 @@ _SIGS = {
     "mhppo_record_work_bytes": (I64, [I64, I32]),
     "mhppo_record_begin": (I32, [P, I64, I32, P, P, P, P]),
     "mhppo_record_step": (I32, [I64, I32, I32, I32] + [P] * 12),
+    "mhppo_record_step_done": (I32, [I64, I32, I32, I32] + [P] * 14),
+    "mhppo_ragged_work_bytes": (I64, [I64]),
+    "mhppo_ragged_plan": (I32, [P, P, P, P, I64, I32, I32, P, P, P, P, P]),
+    "mhppo_returns_scan_tm_len": (I32, [P, P, I64, I32, F64, P, P]),
+    "mhppo_gae_tm_len": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, P, I64, I32, F64, F64, P, P, P, P]),
+    "mhppo_bucket_scatter_ragged": (I32, [P, P, P, I64, I32] + [P] * 9),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }
@@ -184,6 +190,12 @@ def gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_
     .gae_targets_tm), so a run with the knob off can be shown never to reach it."""
     return check(lib().mhppo_gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm, value_tm,
                                     stream))
+
+
+def gae_tm_len(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm, value_tm, len_rec, stream):
+    """mhppo_gae_tm_len, checked (mhppo.rollout.gae_targets_tm with len_rec: the ragged buckets only)."""
+    return check(lib().mhppo_gae_tm_len(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm,
+                                        value_tm, len_rec, stream))
 
 
 # The streaming evaluation statistics' entry points, checked: the one place each is called from

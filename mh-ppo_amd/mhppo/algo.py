@@ -224,7 +224,7 @@ class Algo_PPO:
         self.grad_norms = []
         self._pending_norms = []  # (pinned [10, 2H] norms, event, iteration, head names)
         self._norms_dev = None    # update()'s (norms tensor, head names) of the current iteration
-        self._external = None     # train_external's ((M, T), ExternalRollout): its buffers are allocated once
+        self._external = None     # train_external's ((M, T, early_end), ExternalRollout): its buffers are allocated once
 
     def nets(self):
         return [self.actor_net_cross, self.actor_net_wait, self.actor_net_choice, self.critic_net_cross,
@@ -439,7 +439,7 @@ class Algo_PPO:
             self._after_collect(ep)
         self._finish_train()
 
-    def train_external(self, sim, nb_loop, M, T=None):
+    def train_external(self, sim, nb_loop, M, T=None, early_end=False, check_every=None):
         """train() with the rollout replaced (opt-in, beyond the reference): every iteration plays one
         episode of M parallel streams in `sim` -- anything with reset() -> obs float32 [M, obs_dim] and
         step(actions float64 [M, 2S]) -> (obs, rew, rew_light, ...) on this algo's device -- through
@@ -447,21 +447,24 @@ class Algo_PPO:
         rollout.iteration) and the env's env_id_offset as the first global env id; then the bucketing
         and everything train() does from update() on.  The algo's own env is the config carrier only
         (it may have n_envs = 1) and is not touched: no rollout.reset().  Episodes have the fixed length
-        T (default: the env's max_episode); a simulator that ends one early keeps emitting rows and
-        rewards up to T.  Under data parallelism every rank feeds its own simulator shard."""
+        T (default: the env's max_episode) and the simulator's done is ignored, unless early_end=True:
+        then step's fourth value is the per-stream done, the step that first reports it is the stream's
+        last and terminal, and the buckets are ragged (ExternalRollout(early_end=True); check_every=n
+        lets the host stop an episode once every stream has ended, at one read every n steps).  Under
+        data parallelism every rank feeds its own simulator shard."""
         from .external import ExternalRollout
         r = self.rollout
         r.fix_bucket = self.fix_bucket
         lam = getattr(self, "gae_lambda", None)
         r.gae = None if lam is None else (self.critic_net_cross, self.critic_net_wait, self.gamma, lam)
-        key = (int(M), int(T or self.max_steps))
+        key = (int(M), int(T or self.max_steps), bool(early_end))
         if getattr(self, "_external", None) is None or self._external[0] != key:
-            self._external = (key, ExternalRollout(self.policy(), key[0], T=key[1]))
+            self._external = (key, ExternalRollout(self.policy(), key[0], T=key[1], early_end=key[2]))
         ext = self._external[1]
         ext.session.first_env = int(self.venv.cfg.env_id_offset)
         for ep in range(nb_loop):
             ext.session.seed = int(r.seed)
-            r.batch = ext.collect(sim, r.iteration)
+            r.batch = ext.collect(sim, r.iteration, check_every=check_every)
             r.iteration += 1
             r.cross, r.wait, r.choice = bucket_segments(r.batch, fix_bucket=r.fix_bucket, status=ext.status,
                                                         gae=r.gae)

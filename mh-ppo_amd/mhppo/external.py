@@ -9,13 +9,18 @@ reward record and the NaN-propagating episodic minimum of reward_light -- is the
 it returns has the fields RolloutGPU.collect returns and goes to bucket_segments unchanged; driven by
 a VecCrosswalk it is the collector's batch bit for bit.
 
-Episodes have the fixed length T, as in the collector and the reference's drivers: the time limit is
-terminal and nothing else is.  A simulator that ends an episode early must keep emitting rows and
-rewards up to T; variable-length episodes are not supported.
+By default episodes have the fixed length T, as in the collector and the reference's drivers: the time
+limit is terminal and nothing else is, and a simulator's `done` is ignored.  ExternalRollout(early_end=
+True) takes the per-stream `done` a vectorised simulator returns: the step that first reports it is the
+stream's last, terminal exactly as the time limit is (V = 0 after it, no bootstrap), and nothing of the
+later steps reaches a bucket row, a return, ep_min or a reward sum (mhppo_record_step_done and the ragged
+bucketing, mhppo.rollout.bucket_segments_ragged_native).  Out of scope: auto-reset or several episodes
+per stream and iteration (the choice head is one decision per episode), bootstrapping from V(s_L) at a
+truncation, and a per-slot done.
 
-record_begin_torch / record_step_torch restate the two native calls in torch ops on any device: their
-executable specification and the CPU path (ExternalRollout(native=False) runs them instead of the
-two launches; the sampling itself has no CPU path, so the class needs the GPU either way).
+record_begin_torch / record_step_torch / record_step_done_torch restate the native calls in torch ops on
+any device: their executable specification and the CPU path (ExternalRollout(native=False) runs them
+instead of the launches; the sampling itself has no CPU path, so the class needs the GPU either way).
 """
 import torch
 
@@ -64,6 +69,18 @@ def record_step_torch(t, act, logp, feat_c, rew, rew_light, rec_of, obs_c_tm, ac
     ep_min.copy_(torch.where(m != m, m, torch.where(x != x, x, torch.where(x < m, x, m))))
 
 
+def record_step_done_torch(t, act, logp, feat_c, rew, rew_light, rec_of, obs_c_tm, act_tm, logp_tm, rew_tm, ep_min,
+                           done, len):
+    """mhppo_record_step_done in torch ops, in place: record_step_torch's records for every segment,
+    finished or not; ep_min only for the segments of streams that were running on entry (len[r] == 0);
+    len[r] = t + 1 for the running streams with done[r] != 0.  done bool / uint8 [M], len int32 [M]."""
+    live = len == 0
+    before = ep_min.clone()
+    record_step_torch(t, act, logp, feat_c, rew, rew_light, rec_of, obs_c_tm, act_tm, logp_tm, rew_tm, ep_min)
+    ep_min.copy_(torch.where(live[:, None], ep_min, before))
+    len.copy_(torch.where(live & (done.reshape(-1) != 0), torch.full_like(len, int(t) + 1), len))
+
+
 class ExternalRollout:
     """One episode of M parallel streams whose rows come from a simulator outside the library.
 
@@ -80,10 +97,19 @@ class ExternalRollout:
         cross, wait, choice = bucket_segments(ext.batch(), status=ext.status)
 
     or ext.collect(sim, iteration) for a `sim` with reset() -> obs and step(actions) -> (obs, rew,
-    rew_light, ...).  Episodes have the fixed length T: the time limit is terminal, and a simulator that
-    ends an episode early must keep emitting rows and rewards up to T."""
+    rew_light, ...).  By default episodes have the fixed length T: the time limit is terminal and a
+    simulator's done is ignored.
 
-    def __init__(self, policy, M, T=80, seed=0, first_env=0, compact=None, native=True):
+    early_end=True: record(rew, rew_light, done) takes done, a bool / uint8 [M] device tensor, one flag
+    per stream (all S slots of a stream share its length).  The step that first reports done is the
+    stream's last (length L = t + 1) and terminal; a done raised again later is ignored, and the
+    simulator may go on being stepped for finished streams: their rows are ignored.  self.len int32 [M]
+    holds the lengths, 0 for a stream still running.  batch() may then be taken after any k >= 1
+    recorded steps -- streams still running are cut at k, which is terminal as T is -- and carries len
+    and steps = k, which send bucket_segments down its ragged path.  The policy noise is a function of
+    (seed, iteration, t, env) alone, so a stream's draws do not depend on which others have ended."""
+
+    def __init__(self, policy, M, T=80, seed=0, first_env=0, compact=None, native=True, early_end=False):
         if policy.variant == "4cars2":
             raise ValueError("4cars2 is an env-level variant only: the reference has no driver for it "
                              "(RolloutGPU refuses it too)")
@@ -95,6 +121,7 @@ class ExternalRollout:
         if M < 0 or T < 1:
             raise ValueError(f"ExternalRollout needs M >= 0 and T >= 1, not M = {M}, T = {T}")
         self.policy, self.M, self.T, self.native, self.compact = policy, M, T, bool(native), bool(compact)
+        self.early_end = bool(early_end)
         self.N, self.S, self.P = M, policy.n_slots, policy.nb_ped
         if M * self.S > 2**31 - 1:
             raise ValueError("ExternalRollout: M S > 2^31 - 1")
@@ -112,6 +139,7 @@ class ExternalRollout:
         self.ep_min = z((M, S), torch.float64)
         self.rec_buf = z(M * S + M + 1, torch.int32) if self.compact else None  # segment ranks | per-row prefix
         self.rec_of = self.rec_buf[:M * S] if self.compact else None
+        self.len = z(M, torch.int32) if self.early_end else None  # the streams' lengths, 0: still running
         self.status = z(1, torch.int32)  # NaN flags of the policy draws, for bucket_segments(status=...)
         self._work = z(max(1, int(_lib.lib().mhppo_record_work_bytes(M, S)) // 8), torch.float64)
         self._t = None        # the step act() was last called for
@@ -144,6 +172,8 @@ class ExternalRollout:
             self.ep_min.copy_(ep_min)
             if self.compact:
                 self.rec_buf.copy_(rec)
+        if self.early_end:
+            self.len.zero_()
         self._t, self._recorded, self._begun = None, -1, True
         return d
 
@@ -165,9 +195,11 @@ class ExternalRollout:
         self._t = t
         return actions
 
-    def record(self, rew, rew_light):
+    def record(self, rew, rew_light, done=None):
         """Record the step act() was last called for with the simulator's rew / rew_light, [M, S] tensors
-        on the device (converted to float64).  Steps are recorded once each, in order from 0."""
+        on the device (converted to float64).  Steps are recorded once each, in order from 0.  With
+        early_end the step's done, a bool / uint8 [M] tensor on the device, is required; without it,
+        passing done raises."""
         if self._t is None:
             raise ValueError("ExternalRollout.record before act")
         if self._t == self._recorded:
@@ -180,43 +212,74 @@ class ExternalRollout:
                     or not x.is_floating_point()):
                 raise ValueError(f"ExternalRollout.record takes {name} as a floating-point [{self.M}, {self.S}] "
                                  f"tensor on {self.device}")
+        if not self.early_end and done is not None:
+            raise ValueError("ExternalRollout.record takes done with early_end=True only")
+        if self.early_end:
+            if (not torch.is_tensor(done) or tuple(done.shape) != (self.M,) or done.device != self.device
+                    or done.dtype not in (torch.bool, torch.uint8)):
+                raise ValueError(f"ExternalRollout.record (early_end) takes done as a bool or uint8 [{self.M}] tensor "
+                                 f"on {self.device}")
+            done = done.detach().contiguous()
+            if done.dtype == torch.bool:
+                done = done.view(torch.uint8)
         rew = rew.detach().to(torch.float64).contiguous()
         rew_light = rew_light.detach().to(torch.float64).contiguous()
         s, t = self.session, self._t
         if self.native:
             p = _lib.ptr
+            args = (self.M, self.S, t, self.T, p(s.act), p(s.logp), p(s.feat_c), p(rew), p(rew_light), p(self.rec_of),
+                    p(self.obs_c), p(self.act_tm), p(self.logp_tm), p(self.rew_tm), p(self.ep_min))
             with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().mhppo_record_step(self.M, self.S, t, self.T, p(s.act), p(s.logp), p(s.feat_c),
-                                                        p(rew), p(rew_light), p(self.rec_of), p(self.obs_c),
-                                                        p(self.act_tm), p(self.logp_tm), p(self.rew_tm),
-                                                        p(self.ep_min), self._st()))
+                if self.early_end:
+                    _lib.check(_lib.lib().mhppo_record_step_done(*args, p(done), p(self.len), self._st()))
+                else:
+                    _lib.check(_lib.lib().mhppo_record_step(*args, self._st()))
         else:
             NS = self.M * self.S
-            record_step_torch(t, s.act, s.logp, s.feat_c, rew, rew_light, self.rec_of, self.obs_c.view(self.T, NS, NF_C),
-                              self.act_tm.view(self.T, NS), self.logp_tm.view(self.T, NS), self.rew_tm.view(self.T, NS),
-                              self.ep_min)
+            recs = (self.obs_c.view(self.T, NS, NF_C), self.act_tm.view(self.T, NS), self.logp_tm.view(self.T, NS),
+                    self.rew_tm.view(self.T, NS), self.ep_min)
+            if self.early_end:
+                record_step_done_torch(t, s.act, s.logp, s.feat_c, rew, rew_light, self.rec_of, *recs, done, self.len)
+            else:
+                record_step_torch(t, s.act, s.logp, s.feat_c, rew, rew_light, self.rec_of, *recs)
         self._recorded = t
 
     def batch(self):
-        """The RolloutBatch of the episode, with the fields RolloutGPU.collect returns (N = M)."""
-        if not self._begun or self._recorded != self.T - 1:
+        """The RolloutBatch of the episode, with the fields RolloutGPU.collect returns (N = M); with
+        early_end, after any k >= 1 recorded steps, also len (int32 [M]) and steps = k."""
+        if not self._begun or (self._recorded < 0 if self.early_end else self._recorded != self.T - 1):
             raise ValueError(f"ExternalRollout.batch: {self._recorded + 1} of {self.T} steps recorded")
         d = self.session.decision
+        ragged = dict(len=self.len, steps=self._recorded + 1) if self.early_end else {}
         views = {} if self.compact else dict(obs_c=self.obs_c.permute(1, 2, 0, 3), act=self.act_tm.permute(1, 2, 0),
                                              logp=self.logp_tm.permute(1, 2, 0), rew=self.rew_tm.permute(1, 2, 0))
         return RolloutBatch(feat_d=d.feat_d, probs_d=d.probs, logp_d=d.logp_d, a_d=d.a_d, closest=d.closest, **views,
                             obs_c_tm=self.obs_c, act_tm=self.act_tm, logp_tm=self.logp_tm, rew_tm=self.rew_tm,
                             ep_min=self.ep_min, rec_of=self.rec_of, exist=d.exist, N=self.M, S=self.S, P=self.P,
-                            T=self.T)
+                            T=self.T, **ragged)
 
-    def collect(self, sim, iteration):
+    def collect(self, sim, iteration, check_every=None):
         """The episode loop on `sim`: anything with reset() -> obs and step(actions) -> (obs, rew,
-        rew_light, ...) returning device tensors (a VecCrosswalk qualifies as it is)."""
+        rew_light, ...) returning device tensors (a VecCrosswalk qualifies as it is).  With early_end the
+        step's fourth value is the streams' done.  check_every=n (early_end only): every n steps the
+        host reads whether every stream has ended and stops the episode if so; None: no host read, T
+        steps."""
+        if check_every is not None:
+            if not self.early_end:
+                raise ValueError("ExternalRollout.collect: check_every needs early_end=True")
+            if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
+                raise ValueError(f"ExternalRollout.collect: check_every is None or an integer >= 1, not {check_every!r}")
         with torch.no_grad():
             obs = sim.reset()
             self.begin(obs, iteration)
             for t in range(self.T):
                 actions = self.act(obs, t)
-                obs, rew, rew_light, *_ = sim.step(actions)
-                self.record(rew, rew_light)
+                if self.early_end:
+                    obs, rew, rew_light, done, *_ = sim.step(actions)
+                    self.record(rew, rew_light, done)
+                    if check_every is not None and (t + 1) % check_every == 0 and bool((self.len != 0).all()):
+                        break
+                else:
+                    obs, rew, rew_light, *_ = sim.step(actions)
+                    self.record(rew, rew_light)
         return self.batch()

@@ -373,21 +373,37 @@ class RolloutGPU:
                             exist=self.exist, N=self.N, S=self.S, P=self.P, T=self.T)
 
 
-def returns_scan_tm(rew_tm, gamma=0.99):
+def _check_len_rec(len_rec, B, dev, who):
+    if (not torch.is_tensor(len_rec) or len_rec.dtype != torch.int32 or len_rec.numel() != B or len_rec.device != dev):
+        raise ValueError(f"{who}: len_rec is an int32 [{B}] tensor on the records' device")
+    return len_rec.reshape(B).contiguous()
+
+
+def returns_scan_tm(rew_tm, gamma=0.99, len_rec=None):
     """futur_rewards over time-major records: rew float64 [T, ...] (one segment per column)
-    -> float32 [T, ...]."""
+    -> float32 [T, ...].  len_rec int32 [B] (early episode ends, mhppo_returns_scan_tm_len): column b
+    has len_rec[b] steps (clamped to [0, T]); its scan starts from G = 0 at its last step -- the early
+    end is terminal, as the time limit is -- and the return is 0 from there on."""
     T = rew_tm.shape[0]
     r = rew_tm.reshape(T, -1).contiguous()
     out = torch.empty(r.shape, dtype=torch.float32, device=rew_tm.device)
+    if len_rec is not None:
+        len_rec = _check_len_rec(len_rec, r.shape[1], rew_tm.device, "returns_scan_tm")
     if rew_tm.device.type != "cuda":  # the torch path's CPU form: G_t = r_t + gamma G_{t+1} in float64
         g = torch.zeros_like(r[0])
         for t in range(T - 1, -1, -1):
             g = r[t] + gamma * g
+            if len_rec is not None:  # the specification of the native scan's cut
+                g = torch.where(t < len_rec, g, torch.zeros_like(g))
             out[t] = g.float()
         return out.reshape(rew_tm.shape)
     with torch.cuda.device(rew_tm.device):  # the records' device and its current stream
-        _lib.check(_lib.lib().mhppo_returns_scan_tm(_lib.ptr(r), _lib.ptr(out), r.shape[1], T, gamma,
-                                                    _lib.stream_ptr(device=rew_tm.device)))
+        st = _lib.stream_ptr(device=rew_tm.device)
+        if len_rec is None:
+            _lib.check(_lib.lib().mhppo_returns_scan_tm(_lib.ptr(r), _lib.ptr(out), r.shape[1], T, gamma, st))
+        else:
+            _lib.check(_lib.lib().mhppo_returns_scan_tm_len(_lib.ptr(r), _lib.ptr(out), r.shape[1], T, gamma,
+                                                            _lib.ptr(len_rec), st))
     return out.reshape(rew_tm.shape)
 
 
@@ -402,36 +418,47 @@ def returns_scan(rew, gamma=0.99):
     return out.reshape(rew.shape)
 
 
-def gae_targets_torch(rew_tm, v_tm, gamma, lam, out_dtype=torch.float32):
+def gae_targets_torch(rew_tm, v_tm, gamma, lam, out_dtype=torch.float32, len_rec=None):
     """lambda-return targets R_t = A_t + V_t over time-major records in float64 torch ops (any
     device): the executable specification of mhppo_gae_tm's recurrence (include/mhppo.h, the
     same operation order) and the CPU path.  rew_tm [T, ...] float64, v_tm [T, ...] -> float32
     (out_dtype=torch.float64: the values before the cast).
     A_t = sum_k (gamma lam)^k delta_{t+k}, delta_t = r_t + gamma V_{t+1} - V_t, V_T = 0: no
-    bootstrap past the last step (the episode's time limit is terminal, as in futur_rewards)."""
+    bootstrap past the last step (the episode's time limit is terminal, as in futur_rewards).
+    len_rec int32 (one per column, mhppo_gae_tm_len): column b has len_rec[b] steps; its recurrence
+    starts from A = nv = 0 at its last step and the target is 0 from there on."""
     if rew_tm.shape != v_tm.shape:
         raise ValueError("gae_targets_torch: rew_tm and v_tm differ in shape")
     r, v = rew_tm.double(), v_tm.double()
+    if len_rec is not None:
+        len_rec = _check_len_rec(len_rec, r[0].numel(), r.device, "gae_targets_torch").reshape(r[0].shape)
     out = torch.empty(r.shape, dtype=out_dtype, device=r.device)
     c = float(gamma) * float(lam)
     A = torch.zeros_like(r[0])
     nv = torch.zeros_like(r[0])
+    zero = torch.zeros_like(r[0])
     for t in range(r.shape[0] - 1, -1, -1):
         d = (r[t] + gamma * nv) - v[t]
         A = d + c * A
-        out[t] = (A + v[t]).to(out_dtype)
+        R = A + v[t]
         nv = v[t]
+        if len_rec is not None:
+            live = t < len_rec
+            A, R, nv = torch.where(live, A, zero), torch.where(live, R, zero), torch.where(live, nv, zero)
+        out[t] = R.to(out_dtype)
     return out
 
 
 def gae_targets_tm(obs_tm, rew_tm, critic0, critic1=None, pos=None, bucket=None, gamma=0.99, lam=0.95,
-                   want_value=False):
+                   want_value=False, len_rec=None):
     """mhppo_gae_tm: the critics' forward and the lambda-return scan over time-major records in one
     launch.  obs_tm float32 [T, ..., n_in], rew_tm float64 [T, ...] (B records per step) on the
     critics' GPU; pos int64 [B] / bucket int8 [B] as mhppo_bucket_plan writes them (record b is used
     iff pos[b] >= 0, with critic0 / critic1 for bucket 0 / 1), or pos=None: every record, critic0.
     Returns ret float32 shaped like rew_tm (0 for unused records), with want_value also the critic
-    outputs the scan used.  V is forward_rows' bit for bit; the recurrence is gae_targets_torch's."""
+    outputs the scan used.  V is forward_rows' bit for bit; the recurrence is gae_targets_torch's.
+    len_rec int32 [B] (early episode ends, mhppo_gae_tm_len): record b has len_rec[b] steps; ret and
+    the values are 0 at and beyond them."""
     T = rew_tm.shape[0]
     dev = rew_tm.device
     B = rew_tm[0].numel()
@@ -450,6 +477,8 @@ def gae_targets_tm(obs_tm, rew_tm, critic0, critic1=None, pos=None, bucket=None,
         pos, bucket = pos.contiguous(), bucket.contiguous()
     else:
         bucket = None
+    if len_rec is not None:
+        len_rec = _check_len_rec(len_rec, B, dev, "gae_targets_tm")
     ret = torch.empty((T, B), dtype=torch.float32, device=dev)
     val = torch.empty((T, B), dtype=torch.float32, device=dev) if want_value else None
     d0, keep0 = critic0.mlp_desc()
@@ -457,9 +486,12 @@ def gae_targets_tm(obs_tm, rew_tm, critic0, critic1=None, pos=None, bucket=None,
     if keep0.device != dev or (keep1 is not None and keep1.device != dev):
         raise ValueError("gae_targets_tm: the critics must live on the records' device")
     with torch.cuda.device(dev):
-        _lib.gae_tm(ctypes.byref(d0), ctypes.byref(d1) if d1 is not None else None, _lib.ptr(x), _lib.ptr(r),
-                    _lib.ptr(pos), _lib.ptr(bucket), B, T, float(gamma), float(lam), _lib.ptr(ret), _lib.ptr(val),
-                    _lib.stream_ptr(device=dev))
+        args = (ctypes.byref(d0), ctypes.byref(d1) if d1 is not None else None, _lib.ptr(x), _lib.ptr(r),
+                _lib.ptr(pos), _lib.ptr(bucket), B, T, float(gamma), float(lam), _lib.ptr(ret), _lib.ptr(val))
+        if len_rec is None:
+            _lib.gae_tm(*args, _lib.stream_ptr(device=dev))
+        else:
+            _lib.gae_tm_len(*args, _lib.ptr(len_rec), _lib.stream_ptr(device=dev))
     ret = ret.reshape(rew_tm.shape)
     return (ret, val.reshape(rew_tm.shape)) if want_value else ret
 
@@ -503,7 +535,15 @@ def bucket_segments(batch, fix_bucket=False, status=None, gae=None):
     reward-to-go (gae_targets_tm on the GPU: one launch with the plan's pos / bucket, queued before
     the host read, in place of the returns scan; gae_targets_torch on the torch path).  The choice
     batch keeps its episodic-min target: it is a one-step decision.
+
+    A batch with early episode ends (batch.len set: ExternalRollout(early_end=True)) takes the ragged
+    path, bucket_segments_ragged_native / _torch: a segment of a stream that ended after L steps owns L
+    rows, the dicts gain `rows`, and both paths provide choice["rew_sums"].
     """
+    if getattr(batch, "len", None) is not None:  # early episode ends: ragged buckets
+        if batch.a_d.device.type == "cuda":
+            return bucket_segments_ragged_native(batch, fix_bucket, status, gae=gae)
+        return bucket_segments_ragged_torch(batch, fix_bucket, status, gae=gae)
     if batch.a_d.device.type == "cuda":
         return bucket_segments_native(batch, fix_bucket, status, gae=gae)
     return bucket_segments_torch(batch, fix_bucket, status, gae=gae)
@@ -601,15 +641,7 @@ def bucket_segments_torch(batch, fix_bucket=False, status=None, plan_out=None, g
     `pos` (per record with the compact layout) and the `wait` segment mask (tests).  With gae the
     buckets' `ret` come from gae_targets_torch with V = critic(obs) (torch's forward) per bucket."""
     N, S, P, T = batch.N, batch.S, batch.P, batch.T
-    a_flat = batch.a_d.reshape(N, S * P)
-    if fix_bucket:
-        a_car = batch.a_d.reshape(N, S, P).gather(2, batch.closest.reshape(N, S, 1).long()).reshape(N, S)
-        action_d_i = 2 * a_car.to(torch.int32) - 1
-    else:
-        action_d_i = 2 * a_flat[:, :S].to(torch.int32) - 1  # action_d[i], i < S
-    exist = batch.exist.bool().reshape(-1)
-    cross = exist & (action_d_i <= 0).reshape(-1)
-    wait = exist & (action_d_i > 0).reshape(-1)
+    exist, cross, wait = _segment_masks(batch, fix_bucket)
     NS = N * S
     # Everything is queued before the one host sync, so the GPU runs it while the host waits for
     # the sizes: the returns scan; each segment's bucket position (its rank among its bucket's
@@ -637,19 +669,7 @@ def bucket_segments_torch(batch, fix_bucket=False, status=None, plan_out=None, g
         plan_out.update(pos=pos, wait=wait)
     (both,) = scatter_positions(pos, bucket, (NS + 3,), NS, T, batch.obs_c_tm, batch.act_tm, batch.logp_tm, ret,
                                 batch.rew_tm)
-    seg_all = torch.nonzero_static(exist, size=NS, fill_value=0).squeeze(1)
-    cl = batch.closest.reshape(NS).long().index_select(0, seg_all)
-    base = seg_all * P + cl
-    dc = batch.feat_d.shape[-1]
-    a_sel = batch.a_d.reshape(-1).index_select(0, base)
-    choice = dict(
-        obs=batch.feat_d.reshape(NS * P, dc).index_select(0, base),
-        act=a_sel,
-        logp=batch.logp_d.reshape(-1).index_select(0, base),
-        ret=batch.ep_min.reshape(-1).index_select(0, seg_all).float(),
-    )
-    a_car = batch.a_d.reshape(NS, P).gather(1, batch.closest.reshape(NS, 1).long()).reshape(-1)
-    counts = torch.stack([(exist & (a_car == 0)).sum(), (exist & (a_car == 1)).sum()]).to(torch.float64)
+    choice, counts = _choice_torch(batch, exist)
     sizes = [cc[-1], cw[-1], exist.sum()]
     if status is not None:
         sizes.append(status.reshape(-1)[0].to(torch.int64))
@@ -672,6 +692,297 @@ def bucket_segments_torch(batch, fix_bucket=False, status=None, plan_out=None, g
     choice = {k: v[:n_all] for k, v in choice.items()}
     choice["n_seg"] = n_all
     choice["counts"] = counts  # float64 [2] on the device: (act == 0).sum(), (act == 1).sum()
+    return cross_r, wait_r, choice
+
+
+def _segment_masks(batch, fix_bucket):
+    """The bucket rule in torch ops (bucket_segments): exist, cross, wait as bool [NS]."""
+    N, S, P = batch.N, batch.S, batch.P
+    a_flat = batch.a_d.reshape(N, S * P)
+    if fix_bucket:
+        a_car = batch.a_d.reshape(N, S, P).gather(2, batch.closest.reshape(N, S, 1).long()).reshape(N, S)
+        action_d_i = 2 * a_car.to(torch.int32) - 1
+    else:
+        action_d_i = 2 * a_flat[:, :S].to(torch.int32) - 1  # action_d[i], i < S
+    exist = batch.exist.bool().reshape(-1)
+    cross = exist & (action_d_i <= 0).reshape(-1)
+    wait = exist & (action_d_i > 0).reshape(-1)
+    return exist, cross, wait
+
+
+def _choice_torch(batch, exist):
+    """The choice batch gathered over all NS segment slots (existing ones first: nonzero_static pads
+    with slot 0) and the choice action counts, float64 [2], in torch ops: nothing is read back."""
+    NS, P = batch.N * batch.S, batch.P
+    seg_all = torch.nonzero_static(exist, size=NS, fill_value=0).squeeze(1)
+    cl = batch.closest.reshape(NS).long().index_select(0, seg_all)
+    base = seg_all * P + cl
+    dc = batch.feat_d.shape[-1]
+    a_sel = batch.a_d.reshape(-1).index_select(0, base)
+    choice = dict(
+        obs=batch.feat_d.reshape(NS * P, dc).index_select(0, base),
+        act=a_sel,
+        logp=batch.logp_d.reshape(-1).index_select(0, base),
+        ret=batch.ep_min.reshape(-1).index_select(0, seg_all).float(),
+    )
+    a_car = batch.a_d.reshape(NS, P).gather(1, batch.closest.reshape(NS, 1).long()).reshape(-1)
+    counts = torch.stack([(exist & (a_car == 0)).sum(), (exist & (a_car == 1)).sum()]).to(torch.float64)
+    return choice, counts
+
+
+def _ragged_steps(batch):
+    """(len, k) of a batch with early episode ends, checked."""
+    N, T = batch.N, batch.T
+    k = int(getattr(batch, "steps", T))
+    ln = batch.len
+    if not 1 <= k <= T:
+        raise ValueError(f"a ragged batch has 1 <= steps <= T = {T} recorded steps, not {k}")
+    if not torch.is_tensor(ln) or ln.dtype != torch.int32 or ln.numel() != N or ln.device != batch.a_d.device:
+        raise ValueError(f"a ragged batch's len is an int32 [{N}] tensor on the batch's device")
+    return ln.reshape(N).contiguous(), k
+
+
+def ragged_plan_torch(pos, bucket, rec_of, len, M, S, k):
+    """mhppo_ragged_plan in torch ops (any device): its executable specification.  pos int64 [M S] /
+    bucket int8 [M S] per record column, rec_of int32 [M S] or None, len int32 [M], k recorded steps
+    -> (row0 int64 [M S], len_rec int32 [M S], info int64 [2] = rows_cross, rows_wait).  Nothing is
+    read back."""
+    NS = M * S
+    k = int(k)
+    if k < 1:
+        raise ValueError("ragged_plan_torch: k < 1")
+    ln = len.reshape(M).to(torch.int64)
+    eff = torch.where((ln <= 0) | (ln > k), torch.full_like(ln, k), ln)  # 0: still running, cut at k
+    seg_len = eff.repeat_interleave(S)  # per segment: the S slots of a stream share its length
+    if rec_of is None:
+        len_rec = seg_len
+    else:  # column rec_of[s] holds segment s's record; columns without a record get 0
+        idx = torch.where(rec_of[:NS] >= 0, rec_of[:NS], NS).long()
+        len_rec = torch.zeros(NS + 1, dtype=torch.int64, device=ln.device).scatter_(0, idx, seg_len)[:NS]
+    used = pos >= 0
+    m0, m1 = used & (bucket == 0), used & (bucket != 0)
+    l0, l1 = len_rec * m0, len_rec * m1
+    c0, c1 = torch.cumsum(l0, 0), torch.cumsum(l1, 0)
+    zero = torch.zeros(1, dtype=torch.int64, device=ln.device)
+    rows_cross, rows_wait = (c0[-1:], c1[-1:]) if NS else (zero, zero)
+    w0 = torch.div(rows_cross + 3, 4, rounding_mode="floor") * 4
+    row0 = torch.where(m0, c0 - l0, torch.where(m1, w0 + c1 - l1, torch.full_like(c0, -1)))
+    return row0, len_rec.to(torch.int32), torch.cat([rows_cross, rows_wait])
+
+
+def ragged_plan(pos, bucket, rec_of, len, M, S, k):
+    """mhppo_ragged_plan (CUDA): ragged_plan_torch's three results, queued on the current stream."""
+    NS = M * S
+    dev = pos.device
+    L = _lib.lib()
+    row0 = torch.empty(NS, dtype=torch.int64, device=dev)
+    len_rec = torch.empty(NS, dtype=torch.int32, device=dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    work = torch.empty(max(1, int(L.mhppo_ragged_work_bytes(NS)) // 8), dtype=torch.int64, device=dev)
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        _lib.check(L.mhppo_ragged_plan(p(pos), p(bucket), p(rec_of), p(len), M, S, int(k), p(row0), p(len_rec), p(info),
+                                       p(work), _lib.stream_ptr(device=dev)))
+    return row0, len_rec, info
+
+
+def _ragged_views(both, rows_cross, rows_wait, n_cross, n_wait):
+    w0 = (rows_cross + 3) // 4 * 4
+    keys = ("obs", "act", "logp", "ret", "rew")
+    cross_r = {k: both[k][:rows_cross] for k in keys}
+    wait_r = {k: both[k][w0:w0 + rows_wait] for k in keys}
+    cross_r["n_seg"], wait_r["n_seg"] = n_cross, n_wait
+    cross_r["rows"], wait_r["rows"] = rows_cross, rows_wait
+    return cross_r, wait_r
+
+
+def bucket_segments_ragged_native(batch, fix_bucket=False, status=None, gae=None):
+    """bucket_segments on the GPU for a batch with early episode ends (batch.len int32 [N], batch.steps
+    = k recorded steps; ExternalRollout(early_end=True)): mhppo_bucket_plan, then mhppo_ragged_plan
+    (every segment's first row and length), the reward-to-go or GAE scan cut at the lengths, and ONE
+    ragged scatter of both buckets into the shared buffer that also folds the cross / wait reward
+    sums.  A segment of a stream of length L owns L contiguous rows; the cross rows start at row 0, the
+    wait rows at W0 = rows_cross rounded up to a multiple of 4.  The one host read -- the plan's sizes
+    and status word and the two row counts -- comes before the scatter is queued.  The returned dicts
+    have bucket_segments' keys and `rows`; the choice batch is unchanged (its ret is the ep_min frozen
+    at each stream's end)."""
+    N, S, P, T = batch.N, batch.S, batch.P, batch.T
+    NS = N * S
+    dev = batch.a_d.device
+    L = _lib.lib()
+    ln, k = _ragged_steps(batch)
+    plan = bucket_plan(batch, fix_bucket, status)
+    rec_of = getattr(batch, "rec_of", None)
+    row0, len_rec, rinfo = ragged_plan(plan["pos"], plan["bucket"], None if rec_of is None else rec_of.contiguous(), ln,
+                                       N, S, k)
+    if gae is None:
+        ret_tm = returns_scan_tm(batch.rew_tm, len_rec=len_rec)
+    else:
+        critic_cross, critic_wait, gamma, lam = gae
+        ret_tm = gae_targets_tm(batch.obs_c_tm, batch.rew_tm, critic_cross, critic_wait, plan["pos"], plan["bucket"],
+                                gamma, lam, len_rec=len_rec)
+    info = plan["info"]
+    n = NS * T + 3
+    both = dict(obs=torch.empty(n, NF_C, dtype=torch.float32, device=dev),
+                act=torch.empty(n, dtype=torch.float32, device=dev),
+                logp=torch.empty(n, dtype=torch.float32, device=dev),
+                ret=torch.empty(n, dtype=torch.float32, device=dev),
+                rew=torch.empty(n, dtype=torch.float64, device=dev))
+    one = _lib.BucketDst(*[both[k_].data_ptr() for k_ in ("obs", "act", "logp", "ret", "rew")])
+    dst = (_lib.BucketDst * 2)(one, one)  # cross and wait rows share the buffer (bucket[] keys the sums)
+    srcs = [x.contiguous() for x in (batch.obs_c_tm, batch.act_tm, batch.logp_tm)]
+    rew_tm = batch.rew_tm.contiguous()
+    p = _lib.ptr
+    args = (p(row0), p(plan["bucket"]), p(len_rec), NS, T, *[p(x) for x in srcs], p(ret_tm), p(rew_tm), dst,
+            ctypes.c_void_p(info.data_ptr() + 48), p(plan["work"]), _lib.stream_ptr(device=dev))
+    n_cross, n_wait, n_all, st, rows_cross, rows_wait = torch.cat([info[:4], rinfo]).tolist()  # the one host read
+    if status is not None:
+        if st:
+            status.zero_()
+        raise_if_nan_status(st)
+    with torch.cuda.device(dev):
+        _lib.check(L.mhppo_bucket_scatter_ragged(*args))
+    cross_r, wait_r = _ragged_views(both, rows_cross, rows_wait, n_cross, n_wait)
+    choice = {k_: plan[k_][:n_all] for k_ in ("obs", "act", "logp", "ret")}
+    choice["n_seg"] = n_all
+    f64 = info[4:9].view(torch.float64)
+    choice["counts"] = f64[0:2]
+    choice["rew_sums"] = f64[2:5]
+    return cross_r, wait_r, choice
+
+
+def _tree_torch(v, NT):
+    """block_prims.h's halving tree over NT threads: [..., NT] -> [...]"""
+    v = v.clone()
+    s = NT // 2
+    while s:
+        v[..., :s] = v[..., :s] + v[..., s:2 * s]
+        s //= 2
+    return v[..., 0]
+
+
+def _fold_torch(x, NT, CHAINS):
+    """block_prims.h's fold (k_fold<NT, CHAINS>, or strided_sum + block_sum) of float64 [..., n] in
+    torch ops: element b + u NT + j CHAINS NT goes to chain u of thread b in ascending j, four chains
+    combine as (a0 + a1) + (a2 + a3), then the tree.  Equal order, equal bits."""
+    n, step = x.shape[-1], CHAINS * NT
+    rounds = max(1, -(-n // step))
+    pad = torch.zeros(x.shape[:-1] + (rounds * step,), dtype=torch.float64, device=x.device)
+    pad[..., :n] = x
+    pad = pad.reshape(x.shape[:-1] + (rounds, CHAINS, NT))
+    acc = torch.zeros(x.shape[:-1] + (CHAINS, NT), dtype=torch.float64, device=x.device)
+    for r in range(rounds):
+        acc = acc + pad[..., r, :, :]
+    a = acc[..., 0, :] if CHAINS == 1 else (acc[..., 0, :] + acc[..., 1, :]) + (acc[..., 2, :] + acc[..., 3, :])
+    return _tree_torch(a, NT)
+
+
+def scatter_sums_torch(rew_tm, own, bucket):
+    """The two reward sums of mhppo_bucket_scatter_sums / _scatter_ragged onto zeroed rew_sums, in
+    their order (csrc/ppo_batch.hip k_bucket_scatter at its 1024-thread block): rew_tm float64 [T, NS],
+    own bool [T, NS] (the record is scattered), bucket int8 [NS].  A block is 64 segments x 16 steps;
+    each step's wave adds its 64 records by the xor butterfly, the block its 16 waves in index order;
+    the partials (block y gridDim.x + x) are folded by k_fold<1024, 4>.  -> float64 [2]"""
+    T, NS = rew_tm.shape
+    dev = rew_tm.device
+    gx, gy = -(-NS // 64), -(-T // 16)
+    lanes = torch.arange(64, device=dev)
+    out = []
+    for k in range(2):
+        sel = own & ((bucket != 0) == bool(k))[None, :]
+        r = torch.zeros((gy * 16, gx * 64), dtype=torch.float64, device=dev)
+        r[:T, :NS] = torch.where(sel, 0.0 + rew_tm.float().double(), torch.zeros((), dtype=torch.float64, device=dev))
+        v = r.reshape(gy, 16, gx, 64)
+        for m in (32, 16, 8, 4, 2, 1):
+            v = v + v[..., lanes ^ m]
+        a = torch.zeros((gy, gx), dtype=torch.float64, device=dev)
+        for q in range(16):
+            a = a + v[:, q, :, 0]
+        out.append(0.0 + _fold_torch(a.reshape(gy * gx), 1024, 4))
+    return torch.stack(out)
+
+
+def plan_ep_sum_torch(ep_min, exist):
+    """mhppo_bucket_plan's rew_sums[2] in its order: (double)(float)ep_min of the existing segments
+    through the 256-thread tree per block of 256 segments, the block partials folded by 256 threads
+    with one chain.  -> float64 scalar"""
+    e = torch.where(exist.reshape(-1), ep_min.reshape(-1).float().double(), 0.0)
+    nb = max(1, -(-e.numel() // 256))
+    pad = torch.zeros(nb * 256, dtype=torch.float64, device=e.device)
+    pad[:e.numel()] = e
+    return _fold_torch(_tree_torch(pad.reshape(nb, 256), 256), 256, 1)
+
+
+def _critic_values(critic, obs):
+    """V of observation rows for the torch paths: the native forward on the GPU (the bits the GAE
+    kernel uses), torch's forward on the CPU."""
+    with torch.no_grad():
+        if obs.device.type == "cuda":
+            return critic.forward_rows(obs.contiguous())
+        return critic(obs).reshape(-1)
+
+
+def bucket_segments_ragged_torch(batch, fix_bucket=False, status=None, plan_out=None, gae=None):
+    """bucket_segments_ragged_native in torch ops (any device): its specification and the CPU path.
+    Everything is queued before the one host read.  plan_out: a dict that receives pos, bucket, row0
+    and len_rec (tests).  With gae, V comes from _critic_values on the time-major records."""
+    N, S, P, T = batch.N, batch.S, batch.P, batch.T
+    NS = N * S
+    ln, k = _ragged_steps(batch)
+    exist, cross, wait = _segment_masks(batch, fix_bucket)
+    dev = exist.device
+    cc, cw = torch.cumsum(cross, 0), torch.cumsum(wait, 0)
+    n_cross_d = cc[-1] if NS else torch.zeros((), dtype=torch.int64, device=dev)
+    w0s = torch.div(n_cross_d + 3, 4, rounding_mode="floor") * 4
+    pos = torch.where(cross, cc - 1, torch.where(wait, w0s + cw - 1, -1))
+    bucket = wait.to(torch.int8)
+    rec_of = getattr(batch, "rec_of", None)
+    if rec_of is not None:  # the compact layout: positions and buckets are per record
+        idx = torch.where(rec_of[:NS] >= 0, rec_of[:NS], NS).long()
+        pos = torch.full((NS + 1,), -1, dtype=pos.dtype, device=dev).scatter_(0, idx, pos)[:NS]
+        bucket = torch.zeros(NS + 1, dtype=torch.int8, device=dev).scatter_(0, idx, bucket)[:NS]
+    row0, len_rec, rinfo = ragged_plan_torch(pos, bucket, rec_of, ln, N, S, k)
+    if plan_out is not None:
+        plan_out.update(pos=pos, bucket=bucket, row0=row0, len_rec=len_rec)
+    rew_tm = batch.rew_tm.reshape(T, NS)
+    obs_tm = batch.obs_c_tm.reshape(T, NS, NF_C)
+    if gae is None:
+        ret_tm = returns_scan_tm(rew_tm, len_rec=len_rec)
+    else:
+        v0, v1 = (_critic_values(c, obs_tm.reshape(T * NS, NF_C)).reshape(T, NS) for c in gae[:2])
+        used_len = torch.where(pos >= 0, len_rec, torch.zeros_like(len_rec))
+        ret_tm = gae_targets_torch(rew_tm, torch.where((bucket != 0)[None, :], v1, v0), gae[2], gae[3], len_rec=used_len)
+    # record (t, b) with row0[b] >= 0 and t < len_rec[b] goes to row row0[b] + t; every other record to
+    # a spare row past the buffer's end
+    n = NS * T + 3
+    tt = torch.arange(T, device=dev)[:, None]
+    own = (row0 >= 0)[None, :] & (tt < len_rec[None, :])
+    rows = torch.where(own, row0[None, :] + tt, n).reshape(-1)
+    both = {}
+    for key, x, dt in (("obs", obs_tm, torch.float32), ("act", batch.act_tm, torch.float32),
+                       ("logp", batch.logp_tm, torch.float32), ("ret", ret_tm, torch.float32),
+                       ("rew", rew_tm, torch.float64)):
+        x = x.reshape(T * NS, -1)
+        buf = torch.zeros((n + 1, x.shape[1]), dtype=dt, device=dev)
+        buf[rows] = x
+        both[key] = buf[:n] if key == "obs" else buf[:n, 0]
+    # the reward sums, in the fixed orders of mhppo_bucket_scatter_ragged and mhppo_bucket_plan
+    choice, counts = _choice_torch(batch, exist)
+    rew_sums = torch.cat([scatter_sums_torch(rew_tm, own, bucket), plan_ep_sum_torch(batch.ep_min, exist).reshape(1)])
+    sizes = [n_cross_d, cw[-1] if NS else n_cross_d, exist.sum(), rinfo[0], rinfo[1]]
+    if status is not None:
+        sizes.append(status.reshape(-1)[0].to(torch.int64))
+    sizes = torch.stack(sizes).tolist()  # the one host read
+    if status is not None:
+        if sizes[5]:
+            status.zero_()
+        raise_if_nan_status(sizes[5])
+    n_cross, n_wait, n_all, rows_cross, rows_wait = sizes[:5]
+    cross_r, wait_r = _ragged_views(both, rows_cross, rows_wait, n_cross, n_wait)
+    choice = {k_: v[:n_all] for k_, v in choice.items()}
+    choice["n_seg"] = n_all
+    choice["counts"] = counts
+    choice["rew_sums"] = rew_sums
     return cross_r, wait_r, choice
 
 
