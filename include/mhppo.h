@@ -762,7 +762,8 @@ int mhppo_record_step(int64_t M, int32_t S, int32_t t, int32_t T, const float *a
  * above keep their launches and their bits) ----
  * done is per stream: uint8 [M], what a vectorised simulator's step returns.  If stream r first reports
  * done at step t, step t is its last and its length is L_r = t + 1; done is terminal exactly as the time
- * limit is (V = 0 after it, no bootstrap); a done raised again later is ignored.  len int32 [M]: 0 =
+ * limit is (V = 0 after it; a truncation that bootstraps: the section after this one); a done raised again
+ * later is ignored.  len int32 [M]: 0 =
  * still running (the caller memsets it to 0 when an episode begins), else L_r.  After k recorded steps
  * the effective length of stream r is len[r] ? len[r] : k.  All row offsets are int64. */
 
@@ -825,6 +826,56 @@ int mhppo_bucket_scatter_ragged(const int64_t *row0, const int8_t *bucket, const
                                 int32_t T, const float *obs_tm, const float *act_tm, const float *logp_tm,
                                 const float *ret_tm, const double *rew_tm, const mhppo_bucket_dst *dst,
                                 double *rew_sums, void *work, void *stream);
+
+/* ---- truncation bootstrap of external rollouts (opt-in: ExternalRollout(early_end=True, bootstrap=True);
+ * the calls above keep their launches and their bits) ----
+ * An episode that is cut -- by a simulator's time limit, by a window's end, by taking the batch while the
+ * stream still runs -- has not ended: the value of the state after its last step belongs in its targets.
+ * trunc uint8 [M] (the caller memsets it to 0 when an episode begins) says of a stream that reported done
+ * whether that done was a truncation: it is set from the simulator's `truncated` flag at the step that
+ * first reports done and at no other (if a simulator raises terminated and truncated together, what it
+ * passes as truncated decides).  A stream still running after k recorded steps (k = T included) is cut
+ * at k; that cut is a truncation iff cut_truncates != 0.  A terminal end keeps V = 0 after it.
+ * The successor row s_L of a truncated segment of effective length L: for L < k record L of its column,
+ * which mhppo_record_step_done stored (the caller's contract: the row it recorded at step L for a
+ * truncated stream is the stream's true successor, not a reset row); for L == k the segment's row of
+ * feat_tail float32 [M, S, n_in], the features of the observation after the last recorded step.  The
+ * value is the critic's of the segment's bucket, read when the batch is built: before the iteration's
+ * update, as the GAE values are.  The choice head's episodic-minimum target and the reward sums do not
+ * change. */
+
+/* v_boot of every record column.  Per segment s = r S + i (r < M, i < S):
+ *   col   = rec_of ? rec_of[s] : s; for col < 0 nothing is written
+ *   ended = 1 <= len[r] <= k;  L = ended ? len[r] : k;  tr = ended ? trunc[r] != 0 : cut_truncates != 0
+ *   row   = L < k ? obs_tm[L][col] : feat_tail[s]             (obs_tm float32 [>= k, M S, n_in])
+ *   v_boot[col] = (pos[col] >= 0 && tr && (L < k || feat_tail)) ? critic[bucket[col] != 0](row) : 0.0f
+ * critic[0] = critic0, critic[1] = critic1; the value is bit for bit mhppo_mlp_forward's for that row and
+ * critic.  A row the rule does not select is not read and cannot reach a result (it may hold NaN).
+ * Columns that hold no record are not touched: hand in a zeroed v_boot float32 [M S].  feat_tail NULL:
+ * segments of effective length k are not bootstrapped.  One launch: four-wave blocks, a 32-segment tile
+ * per wave, a grid that is a function of M S alone; no atomics.  M == 0 launches nothing.
+ * MHPPO_EINVAL, nothing written: a critic that is NULL, not kind 0 with one output, or of another n_in
+ * than the other; M < 0, S < 1, M S > 2^31 - 1; k < 1; for M > 0 a NULL pointer other than rec_of and
+ * feat_tail. */
+int mhppo_boot_values(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const int64_t *pos, const int8_t *bucket,
+                      const int32_t *rec_of, const int32_t *len, const uint8_t *trunc, int64_t M, int32_t S,
+                      int32_t k, int32_t cut_truncates, const float *obs_tm, const float *feat_tail, float *v_boot,
+                      void *stream);
+
+/* mhppo_returns_scan_tm_len started from a bootstrap value: column b scans t = L - 1 .. 0 from
+ * G = (double)v_boot[b] instead of 0, L = len_rec[b] clamped to [0, T]: ret[L - 1][b] = (float)(rew[L - 1][b]
+ * + gamma (double)v_boot[b]).  For L == 0 v_boot[b] is not read and the column is all zeros.
+ * v_boot == NULL: mhppo_returns_scan_tm_len's launch and bits. */
+int mhppo_returns_scan_tm_boot(const double *rew, float *ret, int64_t B, int32_t T, double gamma,
+                               const int32_t *len_rec, const float *v_boot, void *stream);
+
+/* mhppo_gae_tm_len started from a bootstrap value: record b's recurrence starts at t = len_rec[b] - 1
+ * from nv = (double)v_boot[b] (the value after its last step) and A = 0, so delta there is
+ * r + gamma v_boot[b] - V.  len_rec is required with v_boot (MHPPO_EINVAL otherwise).  v_boot == NULL:
+ * mhppo_gae_tm_len's launch and bits.  Errors as mhppo_gae_tm. */
+int mhppo_gae_tm_boot(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm, const double *rew_tm,
+                      const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T, double gamma, double lambda,
+                      float *ret_tm, float *value_tm, const int32_t *len_rec, const float *v_boot, void *stream);
 
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);

@@ -25,6 +25,9 @@
 // per-lane mask on `used` where the recurrence runs: at t >= len the record writes 0 and leaves
 // A = nv = 0, so its scan starts from there at t = len - 1 (the early end is terminal).  The wave
 // still walks all T steps; V_t is untouched.
+//
+// k_gae_tm<true, const float *> (mhppo_gae_tm_boot): the same with a bootstrap value per record, a
+// truncated segment's V(s_L): nv = v_boot[b] immediately before step len - 1's delta, A = 0.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,12 +60,18 @@ __device__ __forceinline__ void wave_sync() {
 
 // LDS: [critic0 image][critic1 image, if W1][2 GW input tiles]
 // split (needs W1): unit u is tile u >> 1 with critic u & 1 alone; else unit u is tile u with both
-template <bool LEN>
+// VB: nothing (mhppo_gae_tm / _len), or one const float * (v_boot: mhppo_gae_tm_boot).  A pack, so
+// that without it the kernel is parameter for parameter the function it was before the bootstrap
+// and compiles to the same instructions (profiles/bootstrap/kernel_diff.txt; called from a shared
+// inlined body, k_gae_tm<false> and <true> came out with one v_add_f64's operands exchanged).
+template <bool LEN, typename... VB>
 __global__ void __launch_bounds__(64 * GW)
     k_gae_tm(const float *__restrict__ W0, const float *__restrict__ W1, int n_in, const float *__restrict__ obs_tm,
              const double *__restrict__ rew_tm, const int64_t *__restrict__ pos, const int8_t *__restrict__ bucket,
              int64_t B, int T, double gamma, double lambda, int split, float *__restrict__ ret_tm,
-             float *__restrict__ value_tm, const int32_t *__restrict__ len_rec) {
+             float *__restrict__ value_tm, const int32_t *__restrict__ len_rec, VB... v_boot) {
+  constexpr bool BOOT = sizeof...(VB) != 0;
+  static_assert(!BOOT || LEN, "the bootstrap needs the lengths");
   extern __shared__ float lds[];
   const int tid = threadIdx.x, l = tid & 63, j = l & 31, kh = l >> 5, w = tid >> 6;
   const Img g = img_layout(n_in, 1);
@@ -108,6 +117,10 @@ __global__ void __launch_bounds__(64 * GW)
     wave_sync();  // the previous tile's reads of xc
     stage_x(xc, g, xst, obs_tm + (int64_t)(T - 1) * step, r0, nr, n_in, l);
     double rw = mine && used ? rew_tm[(int64_t)(T - 1) * B + r] : 0.0;
+    double vb = 0.0;  // BOOT: the value after the record's last step
+    if constexpr (BOOT) {
+      if (mine && used) vb = (double)(v_boot, ...)[r];
+    }
     double A = 0.0, nv = 0.0;
 #pragma unroll 1
     for (int t = T - 1; t >= 0; t--) {
@@ -139,6 +152,9 @@ __global__ void __launch_bounds__(64 * GW)
         float ret = 0.0f;
         if (used && (!LEN || t < Lr)) {
           const double v = (double)vf;
+          if constexpr (BOOT) {
+            if (t == Lr - 1) nv = vb;
+          }
           const double d = (rw + gamma * nv) - v;
           A = d + c * A;
           ret = (float)(A + v);
@@ -167,28 +183,36 @@ int check_critic(const mhppo_mlp *m, const char *what) {
   return MHPPO_OK;
 }
 
-LdsLimit g_lds_limit[2];  // k_gae_tm<false / true>'s dynamic LDS above the default 64 KB (wide critics)
+LdsLimit g_lds_limit[3];  // the three instantiations' dynamic LDS above the default 64 KB (wide critics)
 
 int launch(const float *W0, const float *W1, int n_in, const float *obs_tm, const double *rew_tm, const int64_t *pos,
            const int8_t *bucket, int64_t B, int T, double gamma, double lambda, float *ret_tm, float *value_tm,
-           const int32_t *len_rec, hipStream_t s) {
+           const int32_t *len_rec, const float *v_boot, hipStream_t s) {
   const Img g = img_layout(n_in, 1);
   const size_t shm = ((size_t)(W1 ? 2 : 1) * g.size + (size_t)2 * GW * xtile_floats(g)) * sizeof(float);
-  const auto kern = len_rec ? k_gae_tm<true> : k_gae_tm<false>;
-  if (int rc = allow_dynamic_lds(reinterpret_cast<const void *>(kern), shm, g_lds_limit[len_rec ? 1 : 0])) return rc;
   const int split = W1 && n_tiles(B) <= SPLIT_TILES;
   const int64_t units = split ? 2 * n_tiles(B) : n_tiles(B);
   const int nb = (int)std::min<int64_t>((units + GW - 1) / GW, MAX_BLOCKS);
+  if (v_boot) {
+    const auto kern = k_gae_tm<true, const float *>;
+    if (int rc = allow_dynamic_lds(reinterpret_cast<const void *>(kern), shm, g_lds_limit[2])) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64 * GW), shm, s, W0, W1, n_in, obs_tm, rew_tm, pos,
+                       bucket, B, T, gamma, lambda, split, ret_tm, value_tm, len_rec, v_boot);
+    CHECK_HIP(hipGetLastError());
+    return MHPPO_OK;
+  }
+  const auto kern = len_rec ? k_gae_tm<true> : k_gae_tm<false>;
+  if (int rc = allow_dynamic_lds(reinterpret_cast<const void *>(kern), shm, g_lds_limit[len_rec ? 1 : 0])) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64 * GW), shm, s, W0, W1, n_in, obs_tm, rew_tm, pos, bucket, B, T,
                      gamma, lambda, split, ret_tm, value_tm, len_rec);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }
 
-// both entry points: len_rec == NULL is mhppo_gae_tm
+// the three entry points: len_rec == NULL is mhppo_gae_tm, v_boot == NULL mhppo_gae_tm_len
 int gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm, const double *rew_tm,
            const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T, double gamma, double lambda, float *ret_tm,
-           float *value_tm, const int32_t *len_rec, void *stream) {
+           float *value_tm, const int32_t *len_rec, const float *v_boot, void *stream) {
   if (int rc = check_critic(critic0, "critic0")) return rc;
   if (pos || critic1) {
     if (int rc = check_critic(critic1, "critic1")) return rc;
@@ -199,13 +223,14 @@ int gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_
   if (pos && !bucket) return set_error(MHPPO_EINVAL, "mhppo_gae_tm: pos without bucket");
   if (T < 1) return set_error(MHPPO_EINVAL, "mhppo_gae_tm: T < 1");
   if (B < 0) return set_error(MHPPO_EINVAL, "mhppo_gae_tm: B < 0");
+  if (v_boot && !len_rec) return set_error(MHPPO_EINVAL, "mhppo_gae_tm_boot: v_boot without len_rec");
   if (!(gamma >= 0.0 && gamma <= 1.0)) return set_error(MHPPO_EINVAL, "mhppo_gae_tm: gamma outside [0, 1]");
   if (!(lambda >= 0.0 && lambda <= 1.0)) return set_error(MHPPO_EINVAL, "mhppo_gae_tm: lambda outside [0, 1]");
   if (B == 0) return MHPPO_OK;
   if (!obs_tm || !rew_tm || !ret_tm) return set_error(MHPPO_EINVAL, "mhppo_gae_tm: null pointer");
   const float *W0 = critic0->packed, *W1 = pos ? critic1->packed : nullptr;  // pos == NULL: critic0 alone
   const int n_in = critic0->n_in;
-  return launch(W0, W1, n_in, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, len_rec,
+  return launch(W0, W1, n_in, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, len_rec, v_boot,
                 (hipStream_t)stream);
 }
 }  // namespace
@@ -213,12 +238,22 @@ int gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_
 extern "C" int mhppo_gae_tm(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm,
                             const double *rew_tm, const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T,
                             double gamma, double lambda, float *ret_tm, float *value_tm, void *stream) {
-  return gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, nullptr, stream);
+  return gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, nullptr, nullptr,
+                stream);
 }
 
 extern "C" int mhppo_gae_tm_len(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm,
                                 const double *rew_tm, const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T,
                                 double gamma, double lambda, float *ret_tm, float *value_tm, const int32_t *len_rec,
                                 void *stream) {
-  return gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, len_rec, stream);
+  return gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, len_rec, nullptr,
+                stream);
+}
+
+extern "C" int mhppo_gae_tm_boot(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const float *obs_tm,
+                                 const double *rew_tm, const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T,
+                                 double gamma, double lambda, float *ret_tm, float *value_tm, const int32_t *len_rec,
+                                 const float *v_boot, void *stream) {
+  return gae_tm(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lambda, ret_tm, value_tm, len_rec, v_boot,
+                stream);
 }

@@ -1,6 +1,8 @@
 // ppo_batch.hip — from a finished rollout's time-major records to the update's batches (+ C-ABI):
 //   k_returns / k_returns_tm / k_returns_tm_len   the reward-to-go scan (mhppo_returns_scan / _scan_tm /
 //                              _scan_tm_len: a length per column)
+//   k_returns_tm_boot          the same scan started from a bootstrap value per column
+//                              (mhppo_returns_scan_tm_boot)
 //   k_bucket_scatter           both segment-major buckets in one pass over the records, optionally
 //                              with their reward sums, folded by k_fold<1024, 4, add>
 //                              (mhppo_bucket_scatter / _scatter_sums; RAGGED: _scatter_ragged)
@@ -59,6 +61,21 @@ __global__ void __launch_bounds__(TPB)
   const int L = len_rec ? min(max(len_rec[b], 0), T) : T;
   for (int t = T - 1; t >= L; t--) ret[(int64_t)t * B + b] = 0.0f;
   double g = 0.0;
+  for (int t = L - 1; t >= 0; t--) {
+    g = rew[(int64_t)t * B + b] + gamma * g;
+    ret[(int64_t)t * B + b] = (float)g;
+  }
+}
+
+// k_returns_tm_len started from G = v_boot[b] instead of 0 at t = L - 1 (a truncated segment's V(s_L);
+// L == 0: v_boot is not read).  Nothing else differs.
+__global__ void __launch_bounds__(TPB) k_returns_tm_boot(const double *rew, float *ret, int64_t B, int T, double gamma,
+                                                         const int32_t *len_rec, const float *v_boot) {
+  int64_t b = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (b >= B) return;
+  const int L = len_rec ? min(max(len_rec[b], 0), T) : T;
+  for (int t = T - 1; t >= L; t--) ret[(int64_t)t * B + b] = 0.0f;
+  double g = L > 0 ? (double)v_boot[b] : 0.0;
   for (int t = L - 1; t >= 0; t--) {
     g = rew[(int64_t)t * B + b] + gamma * g;
     ret[(int64_t)t * B + b] = (float)g;
@@ -556,6 +573,17 @@ int mhppo_returns_scan_tm_len(const double *rew, float *ret, int64_t B, int32_t 
   if (!rew || !ret || B < 0 || T <= 0) return set_error(MHPPO_EINVAL, "returns_scan_tm_len: bad argument");
   if (B == 0) return MHPPO_OK;
   hipLaunchKernelGGL(k_returns_tm_len, grid_for(B), dim3(TPB), 0, (hipStream_t)stream, rew, ret, B, T, gamma, len_rec);
+  CHECK_HIP(hipGetLastError());
+  return MHPPO_OK;
+}
+
+int mhppo_returns_scan_tm_boot(const double *rew, float *ret, int64_t B, int32_t T, double gamma,
+                               const int32_t *len_rec, const float *v_boot, void *stream) {
+  if (!v_boot) return mhppo_returns_scan_tm_len(rew, ret, B, T, gamma, len_rec, stream);
+  if (!rew || !ret || B < 0 || T <= 0) return set_error(MHPPO_EINVAL, "returns_scan_tm_boot: bad argument");
+  if (B == 0) return MHPPO_OK;
+  hipLaunchKernelGGL(k_returns_tm_boot, grid_for(B), dim3(TPB), 0, (hipStream_t)stream, rew, ret, B, T, gamma, len_rec,
+                     v_boot);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }

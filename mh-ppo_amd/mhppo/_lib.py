@@ -139,6 +139,10 @@ _SIGS = {
     "mhppo_returns_scan_tm_len": (I32, [P, P, I64, I32, F64, P, P]),
     "mhppo_gae_tm_len": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, P, I64, I32, F64, F64, P, P, P, P]),
     "mhppo_bucket_scatter_ragged": (I32, [P, P, P, I64, I32] + [P] * 9),
+    "mhppo_boot_values": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, P, P, I64, I32, I32, I32, P, P, P, P]),
+    "mhppo_returns_scan_tm_boot": (I32, [P, P, I64, I32, F64, P, P, P]),
+    "mhppo_gae_tm_boot": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, P, I64, I32, F64, F64, P, P, P, P,
+                                P]),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }
@@ -196,6 +200,13 @@ def gae_tm_len(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, 
     """mhppo_gae_tm_len, checked (mhppo.rollout.gae_targets_tm with len_rec: the ragged buckets only)."""
     return check(lib().mhppo_gae_tm_len(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm,
                                         value_tm, len_rec, stream))
+
+
+def gae_tm_boot(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm, value_tm, len_rec, v_boot,
+                stream):
+    """mhppo_gae_tm_boot, checked (mhppo.rollout.gae_targets_tm with v_boot: the truncation bootstrap only)."""
+    return check(lib().mhppo_gae_tm_boot(critic0, critic1, obs_tm, rew_tm, pos, bucket, B, T, gamma, lam, ret_tm,
+                                         value_tm, len_rec, v_boot, stream))
 
 
 # The streaming evaluation statistics' entry points, checked: the one place each is called from

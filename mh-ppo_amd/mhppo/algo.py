@@ -224,7 +224,7 @@ class Algo_PPO:
         self.grad_norms = []
         self._pending_norms = []  # (pinned [10, 2H] norms, event, iteration, head names)
         self._norms_dev = None    # update()'s (norms tensor, head names) of the current iteration
-        self._external = None     # train_external's ((M, T, early_end), ExternalRollout): its buffers are allocated once
+        self._external = None     # train_external's (its arguments' key, ExternalRollout): its buffers are allocated once
 
     def nets(self):
         return [self.actor_net_cross, self.actor_net_wait, self.actor_net_choice, self.critic_net_cross,
@@ -439,7 +439,8 @@ class Algo_PPO:
             self._after_collect(ep)
         self._finish_train()
 
-    def train_external(self, sim, nb_loop, M, T=None, early_end=False, check_every=None):
+    def train_external(self, sim, nb_loop, M, T=None, early_end=False, check_every=None, bootstrap=False,
+                       cut_truncates=True):
         """train() with the rollout replaced (opt-in, beyond the reference): every iteration plays one
         episode of M parallel streams in `sim` -- anything with reset() -> obs float32 [M, obs_dim] and
         step(actions float64 [M, 2S]) -> (obs, rew, rew_light, ...) on this algo's device -- through
@@ -450,16 +451,26 @@ class Algo_PPO:
         T (default: the env's max_episode) and the simulator's done is ignored, unless early_end=True:
         then step's fourth value is the per-stream done, the step that first reports it is the stream's
         last and terminal, and the buckets are ragged (ExternalRollout(early_end=True); check_every=n
-        lets the host stop an episode once every stream has ended, at one read every n steps).  Under
-        data parallelism every rank feeds its own simulator shard."""
+        lets the host stop an episode once every stream has ended, at one read every n steps).
+        bootstrap=True (needs early_end=True): step's fifth value is the per-stream truncated, and an
+        episode that was truncated -- at a done flagged so, or still running at the T-step cut unless
+        cut_truncates=False -- starts its cross / wait targets from V(s_L) under the current critics
+        instead of 0 (ExternalRollout(bootstrap=True), bucket_segments(boot=...)).  Under data
+        parallelism every rank feeds its own simulator shard."""
         from .external import ExternalRollout
         r = self.rollout
         r.fix_bucket = self.fix_bucket
         lam = getattr(self, "gae_lambda", None)
         r.gae = None if lam is None else (self.critic_net_cross, self.critic_net_wait, self.gamma, lam)
-        key = (int(M), int(T or self.max_steps), bool(early_end))
+        if bootstrap and not early_end:
+            raise ValueError("train_external: bootstrap=True needs early_end=True")
+        # cut_truncates means nothing without bootstrap: the key is then the one it was
+        key = (int(M), int(T or self.max_steps), bool(early_end)) + ((True, bool(cut_truncates)) if bootstrap else ())
         if getattr(self, "_external", None) is None or self._external[0] != key:
-            self._external = (key, ExternalRollout(self.policy(), key[0], T=key[1], early_end=key[2]))
+            self._external = (key, ExternalRollout(self.policy(), key[0], T=key[1], early_end=key[2],
+                                                   bootstrap=bool(bootstrap), cut_truncates=bool(cut_truncates)))
+        # the critics are read when the buckets are built, before the iteration's update
+        boot = (self.critic_net_cross, self.critic_net_wait) if bootstrap else None
         ext = self._external[1]
         ext.session.first_env = int(self.venv.cfg.env_id_offset)
         for ep in range(nb_loop):
@@ -467,7 +478,7 @@ class Algo_PPO:
             r.batch = ext.collect(sim, r.iteration, check_every=check_every)
             r.iteration += 1
             r.cross, r.wait, r.choice = bucket_segments(r.batch, fix_bucket=r.fix_bucket, status=ext.status,
-                                                        gae=r.gae)
+                                                        gae=r.gae, boot=boot)
             self._after_collect(ep, reset_env=False)
         self._finish_train()
 

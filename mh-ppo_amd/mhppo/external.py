@@ -14,9 +14,16 @@ limit is terminal and nothing else is, and a simulator's `done` is ignored.  Ext
 True) takes the per-stream `done` a vectorised simulator returns: the step that first reports it is the
 stream's last, terminal exactly as the time limit is (V = 0 after it, no bootstrap), and nothing of the
 later steps reaches a bucket row, a return, ep_min or a reward sum (mhppo_record_step_done and the ragged
-bucketing, mhppo.rollout.bucket_segments_ragged_native).  Out of scope: auto-reset or several episodes
-per stream and iteration (the choice head is one decision per episode), bootstrapping from V(s_L) at a
-truncation, and a per-slot done.
+bucketing, mhppo.rollout.bucket_segments_ragged_native).
+
+ExternalRollout(early_end=True, bootstrap=True) tells a truncation from an end (Gymnasium's terminated /
+truncated pair, a T-step window cut out of a longer scene): record takes a second per-stream flag,
+`truncated`, read at the step that first reports done, and a stream still running when the batch is
+taken is cut at k steps, which is a truncation iff cut_truncates (the default).  The targets of a
+truncated segment of length L start from V(s_L) under its bucket's critic instead of 0
+(bucket_segments(boot=...), mhppo_boot_values); s_L is record L of the segment for L < k and a row of
+finish(obs) for L == k.  Out of scope: auto-reset or several episodes per stream and iteration (the
+choice head is one decision per episode) and a per-slot done.
 
 record_begin_torch / record_step_torch / record_step_done_torch restate the native calls in torch ops on
 any device: their executable specification and the CPU path (ExternalRollout(native=False) runs them
@@ -70,15 +77,23 @@ def record_step_torch(t, act, logp, feat_c, rew, rew_light, rec_of, obs_c_tm, ac
 
 
 def record_step_done_torch(t, act, logp, feat_c, rew, rew_light, rec_of, obs_c_tm, act_tm, logp_tm, rew_tm, ep_min,
-                           done, len):
+                           done, len, truncated=None, trunc=None):
     """mhppo_record_step_done in torch ops, in place: record_step_torch's records for every segment,
     finished or not; ep_min only for the segments of streams that were running on entry (len[r] == 0);
-    len[r] = t + 1 for the running streams with done[r] != 0.  done bool / uint8 [M], len int32 [M]."""
+    len[r] = t + 1 for the running streams with done[r] != 0.  done bool / uint8 [M], len int32 [M].
+    With truncated bool / uint8 [M] and trunc uint8 [M] (the truncation bootstrap): trunc[r] =
+    truncated[r] != 0 for exactly the streams whose len this call sets -- the first done; before and
+    after it truncated is ignored."""
+    if (truncated is None) != (trunc is None):
+        raise ValueError("record_step_done_torch: truncated and trunc go together")
     live = len == 0
     before = ep_min.clone()
     record_step_torch(t, act, logp, feat_c, rew, rew_light, rec_of, obs_c_tm, act_tm, logp_tm, rew_tm, ep_min)
     ep_min.copy_(torch.where(live[:, None], ep_min, before))
-    len.copy_(torch.where(live & (done.reshape(-1) != 0), torch.full_like(len, int(t) + 1), len))
+    ends = live & (done.reshape(-1) != 0)
+    len.copy_(torch.where(ends, torch.full_like(len, int(t) + 1), len))
+    if trunc is not None:
+        trunc.copy_(torch.where(ends, (truncated.reshape(-1) != 0).to(trunc.dtype), trunc))
 
 
 class ExternalRollout:
@@ -107,9 +122,25 @@ class ExternalRollout:
     holds the lengths, 0 for a stream still running.  batch() may then be taken after any k >= 1
     recorded steps -- streams still running are cut at k, which is terminal as T is -- and carries len
     and steps = k, which send bucket_segments down its ragged path.  The policy noise is a function of
-    (seed, iteration, t, env) alone, so a stream's draws do not depend on which others have ended."""
+    (seed, iteration, t, env) alone, so a stream's draws do not depend on which others have ended.
 
-    def __init__(self, policy, M, T=80, seed=0, first_env=0, compact=None, native=True, early_end=False):
+    bootstrap=True (needs early_end=True): record(rew, rew_light, done, truncated) also takes truncated,
+    a bool / uint8 [M] device tensor read only at the step where a running stream first reports done:
+    self.trunc uint8 [M] keeps it (if a simulator raises terminated and truncated together, what it
+    passes as truncated decides).  A truncated episode has not ended: bucket_segments(batch, boot=
+    (critic_cross, critic_wait)) starts its segments' targets from V(s_L) instead of 0.  A stream still
+    running when the batch is taken (after k recorded steps, k = T included) is cut at k, which is a
+    truncation iff cut_truncates (default True: a time limit is a truncation).  The successor row s_L
+    of a truncated stream of length L < k is the row handed to act(obs, L): for a truncated stream
+    that row must be its true successor (Gymnasium's final_observation), not a reset row -- a
+    VecCrosswalk keeps stepping finished streams without resetting and satisfies this as it is.  For
+    L == k, finish(obs) takes the rows after the last recorded step; batch() without finish is legal,
+    and then the streams of effective length k are not bootstrapped (v_boot = 0).  With
+    cut_truncates=False and no truncated flag raised the batch's buckets are those of early_end=True
+    alone, bit for bit.  The choice head's target, ep_min and the reward sums do not change."""
+
+    def __init__(self, policy, M, T=80, seed=0, first_env=0, compact=None, native=True, early_end=False,
+                 bootstrap=False, cut_truncates=True):
         if policy.variant == "4cars2":
             raise ValueError("4cars2 is an env-level variant only: the reference has no driver for it "
                              "(RolloutGPU refuses it too)")
@@ -121,7 +152,9 @@ class ExternalRollout:
         if M < 0 or T < 1:
             raise ValueError(f"ExternalRollout needs M >= 0 and T >= 1, not M = {M}, T = {T}")
         self.policy, self.M, self.T, self.native, self.compact = policy, M, T, bool(native), bool(compact)
-        self.early_end = bool(early_end)
+        self.early_end, self.bootstrap, self.cut_truncates = bool(early_end), bool(bootstrap), bool(cut_truncates)
+        if self.bootstrap and not self.early_end:
+            raise ValueError("ExternalRollout: bootstrap=True needs early_end=True")
         self.N, self.S, self.P = M, policy.n_slots, policy.nb_ped
         if M * self.S > 2**31 - 1:
             raise ValueError("ExternalRollout: M S > 2^31 - 1")
@@ -140,6 +173,8 @@ class ExternalRollout:
         self.rec_buf = z(M * S + M + 1, torch.int32) if self.compact else None  # segment ranks | per-row prefix
         self.rec_of = self.rec_buf[:M * S] if self.compact else None
         self.len = z(M, torch.int32) if self.early_end else None  # the streams' lengths, 0: still running
+        self.trunc = z(M, torch.uint8) if self.bootstrap else None  # the first done was a truncation
+        self.feat_tail = None  # finish(): the features of the rows after the last recorded step, [M, S, 13]
         self.status = z(1, torch.int32)  # NaN flags of the policy draws, for bucket_segments(status=...)
         self._work = z(max(1, int(_lib.lib().mhppo_record_work_bytes(M, S)) // 8), torch.float64)
         self._t = None        # the step act() was last called for
@@ -174,6 +209,9 @@ class ExternalRollout:
                 self.rec_buf.copy_(rec)
         if self.early_end:
             self.len.zero_()
+        if self.bootstrap:
+            self.trunc.zero_()
+        self.feat_tail = None
         self._t, self._recorded, self._begun = None, -1, True
         return d
 
@@ -195,13 +233,23 @@ class ExternalRollout:
         self._t = t
         return actions
 
-    def record(self, rew, rew_light, done=None):
+    def _flags(self, x, name):
+        if (not torch.is_tensor(x) or tuple(x.shape) != (self.M,) or x.device != self.device
+                or x.dtype not in (torch.bool, torch.uint8)):
+            raise ValueError(f"ExternalRollout.record takes {name} as a bool or uint8 [{self.M}] tensor on {self.device}")
+        x = x.detach().contiguous()
+        return x.view(torch.uint8) if x.dtype == torch.bool else x
+
+    def record(self, rew, rew_light, done=None, truncated=None):
         """Record the step act() was last called for with the simulator's rew / rew_light, [M, S] tensors
         on the device (converted to float64).  Steps are recorded once each, in order from 0.  With
         early_end the step's done, a bool / uint8 [M] tensor on the device, is required; without it,
-        passing done raises."""
+        passing done raises.  With bootstrap the step's truncated, of the same form, is required too
+        (read only where a running stream first reports done); without it, passing truncated raises."""
         if self._t is None:
             raise ValueError("ExternalRollout.record before act")
+        if self.feat_tail is not None:
+            raise ValueError("ExternalRollout.record after finish")
         if self._t == self._recorded:
             raise ValueError(f"ExternalRollout.record: step {self._t} is recorded already")
         if self._t != self._recorded + 1:
@@ -214,18 +262,19 @@ class ExternalRollout:
                                  f"tensor on {self.device}")
         if not self.early_end and done is not None:
             raise ValueError("ExternalRollout.record takes done with early_end=True only")
+        if not self.bootstrap and truncated is not None:
+            raise ValueError("ExternalRollout.record takes truncated with bootstrap=True only")
         if self.early_end:
-            if (not torch.is_tensor(done) or tuple(done.shape) != (self.M,) or done.device != self.device
-                    or done.dtype not in (torch.bool, torch.uint8)):
-                raise ValueError(f"ExternalRollout.record (early_end) takes done as a bool or uint8 [{self.M}] tensor "
-                                 f"on {self.device}")
-            done = done.detach().contiguous()
-            if done.dtype == torch.bool:
-                done = done.view(torch.uint8)
+            done = self._flags(done, "done")
+        if self.bootstrap:
+            truncated = self._flags(truncated, "truncated")
         rew = rew.detach().to(torch.float64).contiguous()
         rew_light = rew_light.detach().to(torch.float64).contiguous()
         s, t = self.session, self._t
         if self.native:
+            if self.bootstrap:  # the streams whose len the launch below sets: their first done
+                ends = (self.len == 0) & (done != 0)
+                self.trunc.copy_(torch.where(ends, (truncated != 0).to(torch.uint8), self.trunc))
             p = _lib.ptr
             args = (self.M, self.S, t, self.T, p(s.act), p(s.logp), p(s.feat_c), p(rew), p(rew_light), p(self.rec_of),
                     p(self.obs_c), p(self.act_tm), p(self.logp_tm), p(self.rew_tm), p(self.ep_min))
@@ -239,18 +288,42 @@ class ExternalRollout:
             recs = (self.obs_c.view(self.T, NS, NF_C), self.act_tm.view(self.T, NS), self.logp_tm.view(self.T, NS),
                     self.rew_tm.view(self.T, NS), self.ep_min)
             if self.early_end:
-                record_step_done_torch(t, s.act, s.logp, s.feat_c, rew, rew_light, self.rec_of, *recs, done, self.len)
+                record_step_done_torch(t, s.act, s.logp, s.feat_c, rew, rew_light, self.rec_of, *recs, done, self.len,
+                                       truncated, self.trunc)
             else:
                 record_step_torch(t, s.act, s.logp, s.feat_c, rew, rew_light, self.rec_of, *recs)
         self._recorded = t
 
+    def finish(self, obs):
+        """bootstrap only: obs float32 [M, obs_dim], the rows after the last recorded step, so that the
+        streams of effective length k (cut, or ended at the last step by a truncation) can be
+        bootstrapped.  Runs Policy.sample_act on them with the episode's decision and a zero eps tape --
+        the feature rows depend on the observation and the decision alone -- and keeps only feat_c, as
+        self.feat_tail float32 [M, S, 13] in segment layout; the actions and log-probs are discarded.
+        Once per episode, after at least one recorded step; no record after it."""
+        if not self.bootstrap:
+            raise ValueError("ExternalRollout.finish needs bootstrap=True")
+        if not self._begun or self._recorded < 0:
+            raise ValueError("ExternalRollout.finish before any step is recorded")
+        if self.feat_tail is not None:
+            raise ValueError("ExternalRollout.finish was called already")
+        s = self.session
+        s._check(obs, "finish")
+        eps = torch.zeros((self.M, self.S), dtype=torch.float32, device=self.device)
+        r = self.policy.sample_act(obs, s.decision.a_d, s.decision.closest, eps=eps)  # no status: nothing is sampled
+        self.feat_tail = r.feat_c.reshape(self.M, self.S, NF_C)
+
     def batch(self):
         """The RolloutBatch of the episode, with the fields RolloutGPU.collect returns (N = M); with
-        early_end, after any k >= 1 recorded steps, also len (int32 [M]) and steps = k."""
+        early_end, after any k >= 1 recorded steps, also len (int32 [M]) and steps = k; with bootstrap
+        also trunc (uint8 [M]), feat_tail (float32 [M, S, 13], or None without finish: the streams of
+        effective length k are then not bootstrapped) and cut_truncates."""
         if not self._begun or (self._recorded < 0 if self.early_end else self._recorded != self.T - 1):
             raise ValueError(f"ExternalRollout.batch: {self._recorded + 1} of {self.T} steps recorded")
         d = self.session.decision
         ragged = dict(len=self.len, steps=self._recorded + 1) if self.early_end else {}
+        if self.bootstrap:
+            ragged.update(trunc=self.trunc, feat_tail=self.feat_tail, cut_truncates=self.cut_truncates)
         views = {} if self.compact else dict(obs_c=self.obs_c.permute(1, 2, 0, 3), act=self.act_tm.permute(1, 2, 0),
                                              logp=self.logp_tm.permute(1, 2, 0), rew=self.rew_tm.permute(1, 2, 0))
         return RolloutBatch(feat_d=d.feat_d, probs_d=d.probs, logp_d=d.logp_d, a_d=d.a_d, closest=d.closest, **views,
@@ -261,9 +334,9 @@ class ExternalRollout:
     def collect(self, sim, iteration, check_every=None):
         """The episode loop on `sim`: anything with reset() -> obs and step(actions) -> (obs, rew,
         rew_light, ...) returning device tensors (a VecCrosswalk qualifies as it is).  With early_end the
-        step's fourth value is the streams' done.  check_every=n (early_end only): every n steps the
-        host reads whether every stream has ended and stops the episode if so; None: no host read, T
-        steps."""
+        step's fourth value is the streams' done, with bootstrap its fifth their truncated, and finish()
+        gets the rows the last step returned.  check_every=n (early_end only): every n steps the host
+        reads whether every stream has ended and stops the episode if so; None: no host read, T steps."""
         if check_every is not None:
             if not self.early_end:
                 raise ValueError("ExternalRollout.collect: check_every needs early_end=True")
@@ -275,11 +348,17 @@ class ExternalRollout:
             for t in range(self.T):
                 actions = self.act(obs, t)
                 if self.early_end:
-                    obs, rew, rew_light, done, *_ = sim.step(actions)
-                    self.record(rew, rew_light, done)
+                    if self.bootstrap:
+                        obs, rew, rew_light, done, truncated, *_ = sim.step(actions)
+                        self.record(rew, rew_light, done, truncated)
+                    else:
+                        obs, rew, rew_light, done, *_ = sim.step(actions)
+                        self.record(rew, rew_light, done)
                     if check_every is not None and (t + 1) % check_every == 0 and bool((self.len != 0).all()):
                         break
                 else:
                     obs, rew, rew_light, *_ = sim.step(actions)
                     self.record(rew, rew_light)
+            if self.bootstrap:
+                self.finish(obs)
         return self.batch()

@@ -379,19 +379,33 @@ def _check_len_rec(len_rec, B, dev, who):
     return len_rec.reshape(B).contiguous()
 
 
-def returns_scan_tm(rew_tm, gamma=0.99, len_rec=None):
+def _check_v_boot(v_boot, B, dev, who):
+    if (not torch.is_tensor(v_boot) or v_boot.dtype != torch.float32 or v_boot.numel() != B or v_boot.device != dev):
+        raise ValueError(f"{who}: v_boot is a float32 [{B}] tensor on the records' device")
+    return v_boot.reshape(B).contiguous()
+
+
+def returns_scan_tm(rew_tm, gamma=0.99, len_rec=None, v_boot=None):
     """futur_rewards over time-major records: rew float64 [T, ...] (one segment per column)
     -> float32 [T, ...].  len_rec int32 [B] (early episode ends, mhppo_returns_scan_tm_len): column b
     has len_rec[b] steps (clamped to [0, T]); its scan starts from G = 0 at its last step -- the early
-    end is terminal, as the time limit is -- and the return is 0 from there on."""
+    end is terminal, as the time limit is -- and the return is 0 from there on.  v_boot float32 [B]
+    (truncation bootstrap, mhppo_returns_scan_tm_boot): the scan of column b starts from G = v_boot[b]
+    instead, ret[L - 1] = float32(rew[L - 1] + gamma float64(v_boot)); a column of no steps stays 0."""
     T = rew_tm.shape[0]
     r = rew_tm.reshape(T, -1).contiguous()
     out = torch.empty(r.shape, dtype=torch.float32, device=rew_tm.device)
     if len_rec is not None:
         len_rec = _check_len_rec(len_rec, r.shape[1], rew_tm.device, "returns_scan_tm")
+    if v_boot is not None:
+        v_boot = _check_v_boot(v_boot, r.shape[1], rew_tm.device, "returns_scan_tm")
     if rew_tm.device.type != "cuda":  # the torch path's CPU form: G_t = r_t + gamma G_{t+1} in float64
         g = torch.zeros_like(r[0])
+        if v_boot is not None:
+            last = (torch.full_like(v_boot, T, dtype=torch.int32) if len_rec is None else len_rec.clamp(0, T)) - 1
         for t in range(T - 1, -1, -1):
+            if v_boot is not None:  # the specification of the native scan's start
+                g = torch.where(last == t, v_boot.double(), g)
             g = r[t] + gamma * g
             if len_rec is not None:  # the specification of the native scan's cut
                 g = torch.where(t < len_rec, g, torch.zeros_like(g))
@@ -399,7 +413,10 @@ def returns_scan_tm(rew_tm, gamma=0.99, len_rec=None):
         return out.reshape(rew_tm.shape)
     with torch.cuda.device(rew_tm.device):  # the records' device and its current stream
         st = _lib.stream_ptr(device=rew_tm.device)
-        if len_rec is None:
+        if v_boot is not None:
+            _lib.check(_lib.lib().mhppo_returns_scan_tm_boot(_lib.ptr(r), _lib.ptr(out), r.shape[1], T, gamma,
+                                                             _lib.ptr(len_rec), _lib.ptr(v_boot), st))
+        elif len_rec is None:
             _lib.check(_lib.lib().mhppo_returns_scan_tm(_lib.ptr(r), _lib.ptr(out), r.shape[1], T, gamma, st))
         else:
             _lib.check(_lib.lib().mhppo_returns_scan_tm_len(_lib.ptr(r), _lib.ptr(out), r.shape[1], T, gamma,
@@ -418,7 +435,7 @@ def returns_scan(rew, gamma=0.99):
     return out.reshape(rew.shape)
 
 
-def gae_targets_torch(rew_tm, v_tm, gamma, lam, out_dtype=torch.float32, len_rec=None):
+def gae_targets_torch(rew_tm, v_tm, gamma, lam, out_dtype=torch.float32, len_rec=None, v_boot=None):
     """lambda-return targets R_t = A_t + V_t over time-major records in float64 torch ops (any
     device): the executable specification of mhppo_gae_tm's recurrence (include/mhppo.h, the
     same operation order) and the CPU path.  rew_tm [T, ...] float64, v_tm [T, ...] -> float32
@@ -426,18 +443,27 @@ def gae_targets_torch(rew_tm, v_tm, gamma, lam, out_dtype=torch.float32, len_rec
     A_t = sum_k (gamma lam)^k delta_{t+k}, delta_t = r_t + gamma V_{t+1} - V_t, V_T = 0: no
     bootstrap past the last step (the episode's time limit is terminal, as in futur_rewards).
     len_rec int32 (one per column, mhppo_gae_tm_len): column b has len_rec[b] steps; its recurrence
-    starts from A = nv = 0 at its last step and the target is 0 from there on."""
+    starts from A = nv = 0 at its last step and the target is 0 from there on.
+    v_boot float32 (one per column, mhppo_gae_tm_boot; needs len_rec): the recurrence of column b starts
+    from nv = v_boot[b], the value after its last step, instead of 0 (a truncated episode)."""
     if rew_tm.shape != v_tm.shape:
         raise ValueError("gae_targets_torch: rew_tm and v_tm differ in shape")
     r, v = rew_tm.double(), v_tm.double()
+    if v_boot is not None and len_rec is None:
+        raise ValueError("gae_targets_torch: v_boot needs len_rec")
     if len_rec is not None:
         len_rec = _check_len_rec(len_rec, r[0].numel(), r.device, "gae_targets_torch").reshape(r[0].shape)
+    if v_boot is not None:
+        v_boot = _check_v_boot(v_boot, r[0].numel(), r.device, "gae_targets_torch").reshape(r[0].shape).double()
+        last = len_rec.clamp(0, r.shape[0]) - 1
     out = torch.empty(r.shape, dtype=out_dtype, device=r.device)
     c = float(gamma) * float(lam)
     A = torch.zeros_like(r[0])
     nv = torch.zeros_like(r[0])
     zero = torch.zeros_like(r[0])
     for t in range(r.shape[0] - 1, -1, -1):
+        if v_boot is not None:
+            nv = torch.where(last == t, v_boot, nv)
         d = (r[t] + gamma * nv) - v[t]
         A = d + c * A
         R = A + v[t]
@@ -450,7 +476,7 @@ def gae_targets_torch(rew_tm, v_tm, gamma, lam, out_dtype=torch.float32, len_rec
 
 
 def gae_targets_tm(obs_tm, rew_tm, critic0, critic1=None, pos=None, bucket=None, gamma=0.99, lam=0.95,
-                   want_value=False, len_rec=None):
+                   want_value=False, len_rec=None, v_boot=None):
     """mhppo_gae_tm: the critics' forward and the lambda-return scan over time-major records in one
     launch.  obs_tm float32 [T, ..., n_in], rew_tm float64 [T, ...] (B records per step) on the
     critics' GPU; pos int64 [B] / bucket int8 [B] as mhppo_bucket_plan writes them (record b is used
@@ -458,7 +484,8 @@ def gae_targets_tm(obs_tm, rew_tm, critic0, critic1=None, pos=None, bucket=None,
     Returns ret float32 shaped like rew_tm (0 for unused records), with want_value also the critic
     outputs the scan used.  V is forward_rows' bit for bit; the recurrence is gae_targets_torch's.
     len_rec int32 [B] (early episode ends, mhppo_gae_tm_len): record b has len_rec[b] steps; ret and
-    the values are 0 at and beyond them."""
+    the values are 0 at and beyond them.  v_boot float32 [B] (truncation bootstrap, mhppo_gae_tm_boot;
+    needs len_rec): record b's recurrence starts from nv = v_boot[b]."""
     T = rew_tm.shape[0]
     dev = rew_tm.device
     B = rew_tm[0].numel()
@@ -479,6 +506,10 @@ def gae_targets_tm(obs_tm, rew_tm, critic0, critic1=None, pos=None, bucket=None,
         bucket = None
     if len_rec is not None:
         len_rec = _check_len_rec(len_rec, B, dev, "gae_targets_tm")
+    if v_boot is not None:
+        if len_rec is None:
+            raise ValueError("gae_targets_tm: v_boot needs len_rec")
+        v_boot = _check_v_boot(v_boot, B, dev, "gae_targets_tm")
     ret = torch.empty((T, B), dtype=torch.float32, device=dev)
     val = torch.empty((T, B), dtype=torch.float32, device=dev) if want_value else None
     d0, keep0 = critic0.mlp_desc()
@@ -488,7 +519,9 @@ def gae_targets_tm(obs_tm, rew_tm, critic0, critic1=None, pos=None, bucket=None,
     with torch.cuda.device(dev):
         args = (ctypes.byref(d0), ctypes.byref(d1) if d1 is not None else None, _lib.ptr(x), _lib.ptr(r),
                 _lib.ptr(pos), _lib.ptr(bucket), B, T, float(gamma), float(lam), _lib.ptr(ret), _lib.ptr(val))
-        if len_rec is None:
+        if v_boot is not None:
+            _lib.gae_tm_boot(*args, _lib.ptr(len_rec), _lib.ptr(v_boot), _lib.stream_ptr(device=dev))
+        elif len_rec is None:
             _lib.gae_tm(*args, _lib.stream_ptr(device=dev))
         else:
             _lib.gae_tm_len(*args, _lib.ptr(len_rec), _lib.stream_ptr(device=dev))
@@ -509,7 +542,7 @@ def raise_if_nan_status(st):
         raise _lib.MhppoNaNError(f"NaN policy output sampled ({what}): the reference raises ValueError here")
 
 
-def bucket_segments(batch, fix_bucket=False, status=None, gae=None):
+def bucket_segments(batch, fix_bucket=False, status=None, gae=None, boot=None):
     """Split (env, slot) episode segments into the reference's cross/wait/choice batches.
     fix_bucket=True (opt-in bug fix) buckets car i by ITS closest
     pedestrian's decision action_d[i*P + closest_i] instead of the flat action_d[i].
@@ -539,11 +572,17 @@ def bucket_segments(batch, fix_bucket=False, status=None, gae=None):
     A batch with early episode ends (batch.len set: ExternalRollout(early_end=True)) takes the ragged
     path, bucket_segments_ragged_native / _torch: a segment of a stream that ended after L steps owns L
     rows, the dicts gain `rows`, and both paths provide choice["rew_sums"].
+
+    boot = (critic_cross, critic_wait) (opt-in, ragged batches only: ExternalRollout(bootstrap=True)): a
+    segment whose episode was truncated (batch.trunc at a done, batch.cut_truncates at the cut) starts
+    its reward-to-go or GAE scan from V(s_L) under its bucket's critic instead of 0 (boot_values).
     """
     if getattr(batch, "len", None) is not None:  # early episode ends: ragged buckets
         if batch.a_d.device.type == "cuda":
-            return bucket_segments_ragged_native(batch, fix_bucket, status, gae=gae)
-        return bucket_segments_ragged_torch(batch, fix_bucket, status, gae=gae)
+            return bucket_segments_ragged_native(batch, fix_bucket, status, gae=gae, boot=boot)
+        return bucket_segments_ragged_torch(batch, fix_bucket, status, gae=gae, boot=boot)
+    if boot is not None:
+        raise ValueError("bucket_segments: boot needs a batch with early episode ends (batch.len)")
     if batch.a_d.device.type == "cuda":
         return bucket_segments_native(batch, fix_bucket, status, gae=gae)
     return bucket_segments_torch(batch, fix_bucket, status, gae=gae)
@@ -786,6 +825,99 @@ def ragged_plan(pos, bucket, rec_of, len, M, S, k):
     return row0, len_rec, info
 
 
+def _boot_args(pos, bucket, rec_of, len, trunc, M, S, k, obs_tm, feat_tail, n_in, who):
+    """The checked, contiguous operands of boot_values / boot_values_torch."""
+    NS, k = M * S, int(k)
+    dev = pos.device
+    if k < 1:
+        raise ValueError(f"{who}: k < 1")
+    for name, x, dt, n in (("pos", pos, torch.int64, NS), ("bucket", bucket, torch.int8, NS),
+                           ("len", len, torch.int32, M), ("trunc", trunc, torch.uint8, M)):
+        if not torch.is_tensor(x) or x.dtype != dt or x.numel() != n or x.device != dev:
+            raise ValueError(f"{who}: {name} is a {dt} [{n}] tensor on the records' device")
+    if rec_of is not None and (rec_of.dtype != torch.int32 or rec_of.numel() < NS or rec_of.device != dev):
+        raise ValueError(f"{who}: rec_of is an int32 [{NS}] tensor on the records' device, or None")
+    if (obs_tm.dtype != torch.float32 or obs_tm.device != dev or obs_tm.shape[-1] != n_in
+            or obs_tm.numel() % max(1, NS * n_in) or (NS and obs_tm.numel() // (NS * n_in) < k)):
+        raise ValueError(f"{who}: obs_tm is a float32 [>= {k}, {NS}, {n_in}] tensor on the records' device")
+    if feat_tail is not None and (feat_tail.dtype != torch.float32 or feat_tail.device != dev
+                                  or feat_tail.numel() != NS * n_in):
+        raise ValueError(f"{who}: feat_tail is a float32 [{M}, {S}, {n_in}] tensor on the records' device, or None")
+    c = lambda x: None if x is None else x.contiguous()
+    return (c(pos.reshape(NS)), c(bucket.reshape(NS)), None if rec_of is None else c(rec_of.reshape(-1)[:NS]),
+            c(len.reshape(M)), c(trunc.reshape(M)), c(obs_tm.reshape(-1 if NS else 0, NS, n_in)),
+            None if feat_tail is None else c(feat_tail.reshape(NS, n_in)))
+
+
+def boot_values_torch(critic0, critic1, pos, bucket, rec_of, len, trunc, M, S, k, cut_truncates, obs_tm, feat_tail=None):
+    """mhppo_boot_values in torch ops (any device): its executable specification and the CPU path.
+    Per segment s = r S + i: col = rec_of[s] (s with rec_of None; nothing for col < 0); the stream ended
+    iff 1 <= len[r] <= k, with L = len[r] and the truncation flag trunc[r]; else it was cut at L = k,
+    a truncation iff cut_truncates.  A truncated segment of a used column (pos[col] >= 0) gets
+    v_boot[col] = critic(row), critic1 for bucket[col] != 0 else critic0, row = obs_tm[L, col] for
+    L < k and feat_tail[s] for L == k (None: no bootstrap there); every other column 0.  V comes from
+    _critic_values: mhppo_mlp_forward on the GPU.  Rows the rule does not select are replaced by zeros
+    before the forward.  -> float32 [M S]; nothing is read back."""
+    n_in = critic0.n_in
+    if critic1.n_in != n_in:
+        raise ValueError("boot_values_torch: the critics differ in n_in")
+    pos, bucket, rec_of, ln, trunc, obs, tail = _boot_args(pos, bucket, rec_of, len, trunc, M, S, k, obs_tm, feat_tail,
+                                                           n_in, "boot_values_torch")
+    NS, k = M * S, int(k)
+    dev = pos.device
+    s = torch.arange(NS, device=dev)
+    r = torch.div(s, S, rounding_mode="floor")
+    col = s if rec_of is None else rec_of.long()
+    has = col >= 0
+    colc = col.clamp_min(0)
+    lr = ln.long().index_select(0, r)
+    ended = (lr >= 1) & (lr <= k)
+    L = torch.where(ended, lr, torch.full_like(lr, k))
+    tr = torch.where(ended, trunc.index_select(0, r) != 0, torch.full_like(ended, bool(cut_truncates)))
+    rec = L < k
+    sel = has & (pos.index_select(0, colc) >= 0) & tr & (rec | (tail is not None))
+    b1 = bucket.index_select(0, colc) != 0
+    rows = obs[torch.where(rec, L, torch.zeros_like(L)), colc]
+    if tail is not None:
+        rows = torch.where(rec[:, None], rows, tail)
+    rows = torch.where(sel[:, None], rows, torch.zeros((), dtype=torch.float32, device=dev))
+    v0, v1 = _critic_values(critic0, rows).float(), _critic_values(critic1, rows).float()
+    v = torch.where(sel, torch.where(b1, v1, v0), torch.zeros((), dtype=torch.float32, device=dev))
+    out = torch.zeros(NS + 1, dtype=torch.float32, device=dev)
+    return out.scatter_(0, torch.where(has, col, torch.full_like(col, NS)), v)[:NS]
+
+
+def boot_values(critic0, critic1, pos, bucket, rec_of, len, trunc, M, S, k, cut_truncates, obs_tm, feat_tail=None):
+    """mhppo_boot_values (CUDA): boot_values_torch's result in one launch on the current stream, V bit
+    for bit forward_rows'."""
+    n_in = critic0.n_in
+    pos, bucket, rec_of, ln, trunc, obs, tail = _boot_args(pos, bucket, rec_of, len, trunc, M, S, k, obs_tm, feat_tail,
+                                                           n_in, "boot_values")
+    dev = pos.device
+    d0, keep0 = critic0.mlp_desc()
+    d1, keep1 = critic1.mlp_desc()
+    if dev.type != "cuda" or keep0.device != dev or keep1.device != dev:
+        raise ValueError("boot_values: the critics must live on the records' GPU")
+    v_boot = torch.zeros(M * S, dtype=torch.float32, device=dev)
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mhppo_boot_values(ctypes.byref(d0), ctypes.byref(d1), p(pos), p(bucket), p(rec_of), p(ln),
+                                                p(trunc), M, S, int(k), int(bool(cut_truncates)), p(obs), p(tail),
+                                                p(v_boot), _lib.stream_ptr(device=dev)))
+    return v_boot
+
+
+def _batch_boot(batch, boot, plan_pos, plan_bucket, rec_of, ln, k, native):
+    """v_boot of a ragged batch under boot = (critic_cross, critic_wait), or None: no boot, or a batch
+    without the truncation flags (ExternalRollout without bootstrap)."""
+    trunc = getattr(batch, "trunc", None)
+    if boot is None or trunc is None:
+        return None
+    f = boot_values if native else boot_values_torch
+    return f(boot[0], boot[1], plan_pos, plan_bucket, rec_of, ln, trunc, batch.N, batch.S, k,
+             getattr(batch, "cut_truncates", True), batch.obs_c_tm, getattr(batch, "feat_tail", None))
+
+
 def _ragged_views(both, rows_cross, rows_wait, n_cross, n_wait):
     w0 = (rows_cross + 3) // 4 * 4
     keys = ("obs", "act", "logp", "ret", "rew")
@@ -796,7 +928,7 @@ def _ragged_views(both, rows_cross, rows_wait, n_cross, n_wait):
     return cross_r, wait_r
 
 
-def bucket_segments_ragged_native(batch, fix_bucket=False, status=None, gae=None):
+def bucket_segments_ragged_native(batch, fix_bucket=False, status=None, gae=None, boot=None):
     """bucket_segments on the GPU for a batch with early episode ends (batch.len int32 [N], batch.steps
     = k recorded steps; ExternalRollout(early_end=True)): mhppo_bucket_plan, then mhppo_ragged_plan
     (every segment's first row and length), the reward-to-go or GAE scan cut at the lengths, and ONE
@@ -805,7 +937,9 @@ def bucket_segments_ragged_native(batch, fix_bucket=False, status=None, gae=None
     wait rows at W0 = rows_cross rounded up to a multiple of 4.  The one host read -- the plan's sizes
     and status word and the two row counts -- comes before the scatter is queued.  The returned dicts
     have bucket_segments' keys and `rows`; the choice batch is unchanged (its ret is the ep_min frozen
-    at each stream's end)."""
+    at each stream's end).  boot = (critic_cross, critic_wait) on a batch with trunc: mhppo_boot_values is
+    queued after the ragged plan and the scan that runs starts every truncated segment from its v_boot
+    (mhppo_returns_scan_tm_boot / mhppo_gae_tm_boot); the host read stays the only one."""
     N, S, P, T = batch.N, batch.S, batch.P, batch.T
     NS = N * S
     dev = batch.a_d.device
@@ -813,14 +947,15 @@ def bucket_segments_ragged_native(batch, fix_bucket=False, status=None, gae=None
     ln, k = _ragged_steps(batch)
     plan = bucket_plan(batch, fix_bucket, status)
     rec_of = getattr(batch, "rec_of", None)
-    row0, len_rec, rinfo = ragged_plan(plan["pos"], plan["bucket"], None if rec_of is None else rec_of.contiguous(), ln,
-                                       N, S, k)
+    rec_of = None if rec_of is None else rec_of.contiguous()
+    row0, len_rec, rinfo = ragged_plan(plan["pos"], plan["bucket"], rec_of, ln, N, S, k)
+    v_boot = _batch_boot(batch, boot, plan["pos"], plan["bucket"], rec_of, ln, k, native=True)
     if gae is None:
-        ret_tm = returns_scan_tm(batch.rew_tm, len_rec=len_rec)
+        ret_tm = returns_scan_tm(batch.rew_tm, len_rec=len_rec, v_boot=v_boot)
     else:
         critic_cross, critic_wait, gamma, lam = gae
         ret_tm = gae_targets_tm(batch.obs_c_tm, batch.rew_tm, critic_cross, critic_wait, plan["pos"], plan["bucket"],
-                                gamma, lam, len_rec=len_rec)
+                                gamma, lam, len_rec=len_rec, v_boot=v_boot)
     info = plan["info"]
     n = NS * T + 3
     both = dict(obs=torch.empty(n, NF_C, dtype=torch.float32, device=dev),
@@ -922,10 +1057,11 @@ def _critic_values(critic, obs):
         return critic(obs).reshape(-1)
 
 
-def bucket_segments_ragged_torch(batch, fix_bucket=False, status=None, plan_out=None, gae=None):
+def bucket_segments_ragged_torch(batch, fix_bucket=False, status=None, plan_out=None, gae=None, boot=None):
     """bucket_segments_ragged_native in torch ops (any device): its specification and the CPU path.
     Everything is queued before the one host read.  plan_out: a dict that receives pos, bucket, row0
-    and len_rec (tests).  With gae, V comes from _critic_values on the time-major records."""
+    and len_rec (and v_boot, when there is one; tests).  With gae, V comes from _critic_values on the
+    time-major records; with boot on a batch with trunc, v_boot from boot_values_torch."""
     N, S, P, T = batch.N, batch.S, batch.P, batch.T
     NS = N * S
     ln, k = _ragged_steps(batch)
@@ -942,16 +1078,20 @@ def bucket_segments_ragged_torch(batch, fix_bucket=False, status=None, plan_out=
         pos = torch.full((NS + 1,), -1, dtype=pos.dtype, device=dev).scatter_(0, idx, pos)[:NS]
         bucket = torch.zeros(NS + 1, dtype=torch.int8, device=dev).scatter_(0, idx, bucket)[:NS]
     row0, len_rec, rinfo = ragged_plan_torch(pos, bucket, rec_of, ln, N, S, k)
+    v_boot = _batch_boot(batch, boot, pos, bucket, rec_of, ln, k, native=False)
     if plan_out is not None:
         plan_out.update(pos=pos, bucket=bucket, row0=row0, len_rec=len_rec)
+        if v_boot is not None:
+            plan_out.update(v_boot=v_boot)
     rew_tm = batch.rew_tm.reshape(T, NS)
     obs_tm = batch.obs_c_tm.reshape(T, NS, NF_C)
     if gae is None:
-        ret_tm = returns_scan_tm(rew_tm, len_rec=len_rec)
+        ret_tm = returns_scan_tm(rew_tm, len_rec=len_rec, v_boot=v_boot)
     else:
         v0, v1 = (_critic_values(c, obs_tm.reshape(T * NS, NF_C)).reshape(T, NS) for c in gae[:2])
         used_len = torch.where(pos >= 0, len_rec, torch.zeros_like(len_rec))
-        ret_tm = gae_targets_torch(rew_tm, torch.where((bucket != 0)[None, :], v1, v0), gae[2], gae[3], len_rec=used_len)
+        ret_tm = gae_targets_torch(rew_tm, torch.where((bucket != 0)[None, :], v1, v0), gae[2], gae[3], len_rec=used_len,
+                                   v_boot=v_boot)
     # record (t, b) with row0[b] >= 0 and t < len_rec[b] goes to row row0[b] + t; every other record to
     # a spare row past the buffer's end
     n = NS * T + 3
