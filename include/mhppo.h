@@ -440,6 +440,22 @@ int mhppo_ppo_diag(const mhppo_mlp *actor, const mhppo_mlp *critic, const float 
                    const void *act, const float *logp_old, const float *ret, double *sums,
                    void *work, void *stream);
 
+/* The KL measurement of the opt-in early stop (Algo_PPO(target_kl=...)): the actor half of
+ * mhppo_ppo_diag alone, for a launch per head and epoch.
+ * Contract: sums float64 [2] is WRITTEN, not accumulated (this rank's rows; the sums add across ranks):
+ *   sums[0] = sum d,  sums[1] = sum (expm1(d) - d),  d = logp_new - logp_old,
+ * bit for bit mhppo_ppo_diag's sums[MHPPO_DIAG_DSUM] and sums[MHPPO_DIAG_K3] for the same actor, rows
+ * and M, whatever critic that call gets: the same grid (a function of M alone), tile-to-wave walk,
+ * per-row terms, per-wave tree, wave order and fold.  One weight image and one forward per tile, two
+ * float64 accumulators; neither a critic nor `ret` is read.
+ * actor->kind 1: act float32 [M]; actor->kind 2: act int32 [M].  work: mhppo_ppo_kl_work_bytes(M)
+ * bytes of device scratch (8-byte aligned, >= 8).  M == 0 writes two zeros and launches nothing else.
+ * MHPPO_EINVAL as mhppo_ppo_diag: an actor of kind 0, n_in outside 1..64, a kind / n_out mismatch, a
+ * NULL pointer, M < 0; a refused call touches nothing. */
+int64_t mhppo_ppo_kl_work_bytes(int64_t M);
+int mhppo_ppo_kl(const mhppo_mlp *actor, const float *X, int64_t M, const void *act,
+                 const float *logp_old, double *sums, void *work, void *stream);
+
 /* ---- GAE(lambda) targets (csrc/mlp_gae.hip; opt-in, beyond the reference, which trains on the
  * Monte-Carlo reward-to-go of mhppo_returns_scan_tm, futur_rewards :658-684) ---- */
 
@@ -593,6 +609,32 @@ typedef struct mhppo_adam_net {
     double beta1, beta2, eps;
 } mhppo_adam_net;
 int mhppo_adam_clip(const mhppo_adam_net *nets, int32_t n_nets, double max_norm, double *norms, void *stream);
+
+/* mhppo_adam_clip with a per-net gate decided on the device (the KL early stop of
+ * Algo_PPO(target_kl=...): the host never reads the KL, so an update's epoch loop has no round trip).
+ * Contract: gates == NULL, or a net whose gate has kl == NULL: the net follows mhppo_adam_clip's
+ * contract bit for bit.  A gated net is OPEN iff *stop == 0 and kl[1] <= limit (a NaN kl closes):
+ *   open:    mhppo_adam_clip's contract bit for bit; *stop stays 0.
+ *   closed:  norms[k] = NaN (a net that was not stepped); *stop = epoch if it was 0 (so a stop is
+ *            sticky and keeps the first epoch); nothing else of the net is read or written: param,
+ *            exp_avg, exp_avg_sq and step keep their bits, grad is not read, the fold is skipped.
+ * The decision is the same in every thread of the net's block: all threads read *stop, a barrier,
+ * then one thread writes it.  kl and stop are DEVICE memory, read when the kernel runs (stream
+ * order: after the mhppo_ppo_kl launch and any all-reduce that fill kl); the gates array is HOST
+ * memory and travels with the table in the kernel arguments (8 x 32 bytes more: 3 664 bytes of the
+ * 4 KB in all).  limit is in the units of kl[1], a SUM over rows (mhppo.ppo.kl_limit: 1.5 tau m):
+ * the kernel never divides.  Nets stay independent and the call deterministic, as mhppo_adam_clip's.
+ * MHPPO_EINVAL: everything mhppo_adam_clip refuses, and a gated net with stop == NULL, epoch < 1 or
+ * limit NaN or < 0 (inf allowed: it never closes on a finite kl); a refused call touches nothing. */
+typedef struct mhppo_adam_gate {
+    const double *kl;  /* device: the 2 doubles of mhppo_ppo_kl (global sums); NULL: this net is not gated */
+    double limit;      /* open iff *stop == 0 and kl[1] <= limit (a NaN kl closes) */
+    int32_t *stop;     /* device word, 0 = running */
+    int32_t epoch;     /* >= 1: written to *stop by the call that first closes the net */
+    int32_t reserved;
+} mhppo_adam_gate;
+int mhppo_adam_clip_gated(const mhppo_adam_net *nets, int32_t n_nets, double max_norm, double *norms,
+                          const mhppo_adam_gate *gates, void *stream);
 
 /* ---- the minibatch shuffle (csrc/batch_shuffle.hip, csrc/batch_shuffle.h; opt-in, beyond the
  * reference, whose epochs are full-batch) ---- */

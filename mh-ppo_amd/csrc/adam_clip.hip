@@ -1,5 +1,6 @@
 // adam_clip.hip — gradient-norm clipping and the Adam step of up to MHPPO_ADAM_MAX_NETS independent
-// nets in one launch (+ C-ABI, mhppo_adam_clip; the arithmetic contract is include/mhppo.h's).
+// nets in one launch (+ C-ABI, mhppo_adam_clip; the arithmetic contract is include/mhppo.h's), and
+// the same launch with a per-net gate decided on the device (mhppo_adam_clip_gated: the KL early stop).
 // One block of 1024 threads per net: it folds the net's squared gradient in the fixed order of
 // block_prims.h (k_fold<1024, 4> over the flat element index, across segment boundaries), forms
 // the clip scale and steps the same net.  A net is 4 673 to 6 338 floats in the product: the launch
@@ -36,6 +37,19 @@ struct Net {
 struct Args {
   Net net[MHPPO_ADAM_MAX_NETS];
 };
+// the gates of mhppo_adam_clip_gated, one per net (kl == nullptr: the net is not gated)
+struct Gate {
+  const double *kl;
+  double limit;
+  int *stop;
+  int epoch;
+};
+struct Gates {
+  Gate g[MHPPO_ADAM_MAX_NETS];
+};
+// the table, the gates, max_norm and norms all travel in the kernel arguments (include/mhppo.h)
+static_assert(sizeof(Args) + sizeof(Gates) + sizeof(double) + sizeof(double *) <= 4096,
+              "adam_clip: the kernel arguments outgrew the 4 KB of a launch");
 
 struct Elem {
   float *p;
@@ -58,8 +72,8 @@ __device__ __forceinline__ Elem locate(const Net &net, int i) {
   return {e.p + o, e.g + o, e.m + o, e.v + o};
 }
 
-__global__ void __launch_bounds__(NT) k_adam_clip(const Args args, double max_norm, double *norms) {
-  const Net &net = args.net[blockIdx.x];
+// The block's work on its net: the fold, the norm, the clip scale, the step (both kernels below).
+__device__ __forceinline__ void clip_and_step(const Net &net, double max_norm, double *norms) {
   const int n = net.n;
   double ss[1] = {strided_sum<NT, CHAINS>(
       [&](int i) {
@@ -99,15 +113,40 @@ __global__ void __launch_bounds__(NT) k_adam_clip(const Args args, double max_no
   }
 }
 
+__global__ void __launch_bounds__(NT) k_adam_clip(const Args args, double max_norm, double *norms) {
+  clip_and_step(args.net[blockIdx.x], max_norm, norms);
+}
+
+// mhppo_adam_clip_gated.  A gated net's block first decides, alike in every thread, whether the net
+// is open: *stop == 0 and kl[1] <= limit (a NaN fails the comparison).  Every thread reads *stop,
+// then the barrier, then thread 0 alone may write it: no thread can read the word after the write.
+// A closed net's block writes norms[k] = NaN, *stop = epoch if it was 0, and leaves: no gradient,
+// parameter, moment or step of the net is read or written.
+__global__ void __launch_bounds__(NT) k_adam_clip_gated(const Args args, double max_norm, double *norms,
+                                                        const Gates gates) {
+  const Gate &gt = gates.g[blockIdx.x];
+  if (gt.kl) {
+    const int stopped = *gt.stop;
+    const bool open = stopped == 0 && gt.kl[1] <= gt.limit;
+    __syncthreads();
+    if (!open) {
+      if (threadIdx.x == 0) {
+        norms[blockIdx.x] = __builtin_nan("");
+        if (stopped == 0) *gt.stop = gt.epoch;
+      }
+      return;
+    }
+  }
+  clip_and_step(args.net[blockIdx.x], max_norm, norms);
+}
+
 }  // namespace
 
-extern "C" int mhppo_adam_clip(const mhppo_adam_net *nets, int32_t n_nets, double max_norm, double *norms,
-                               void *stream) {
-  if (n_nets == 0) return MHPPO_OK;
+// The checks that both entry points share, and the launch table.
+static int build_args(const mhppo_adam_net *nets, int32_t n_nets, double max_norm, const double *norms, Args &args) {
   if (!nets || !norms || n_nets < 0 || n_nets > MHPPO_ADAM_MAX_NETS)
     return set_error(MHPPO_EINVAL, "adam_clip: 0 .. %d nets, a table and norms", MHPPO_ADAM_MAX_NETS);
   if (!(max_norm > 0.0)) return set_error(MHPPO_EINVAL, "adam_clip: max_norm must be > 0 (inf allowed)");
-  Args args = {};
   for (int k = 0; k < n_nets; k++) {
     const mhppo_adam_net &in = nets[k];
     Net &net = args.net[k];
@@ -134,7 +173,35 @@ extern "C" int mhppo_adam_clip(const mhppo_adam_net *nets, int32_t n_nets, doubl
     net.c2 = (float)(1.0 - in.beta2);
     net.eps = (float)in.eps;
   }
+  return MHPPO_OK;
+}
+
+extern "C" int mhppo_adam_clip(const mhppo_adam_net *nets, int32_t n_nets, double max_norm, double *norms,
+                               void *stream) {
+  if (n_nets == 0) return MHPPO_OK;
+  Args args = {};
+  if (int rc = build_args(nets, n_nets, max_norm, norms, args)) return rc;
   hipLaunchKernelGGL(k_adam_clip, dim3(n_nets), dim3(NT), 0, (hipStream_t)stream, args, max_norm, norms);
+  CHECK_HIP(hipGetLastError());
+  return MHPPO_OK;
+}
+
+extern "C" int mhppo_adam_clip_gated(const mhppo_adam_net *nets, int32_t n_nets, double max_norm, double *norms,
+                                     const mhppo_adam_gate *gates, void *stream) {
+  if (!gates) return mhppo_adam_clip(nets, n_nets, max_norm, norms, stream);
+  if (n_nets == 0) return MHPPO_OK;
+  Args args = {};
+  if (int rc = build_args(nets, n_nets, max_norm, norms, args)) return rc;
+  Gates gs = {};
+  for (int k = 0; k < n_nets; k++) {
+    const mhppo_adam_gate &in = gates[k];
+    if (!in.kl) continue;
+    if (!in.stop) return set_error(MHPPO_EINVAL, "adam_clip_gated: net %d is gated without a stop word", k);
+    if (in.epoch < 1) return set_error(MHPPO_EINVAL, "adam_clip_gated: net %d: epoch %d < 1", k, (int)in.epoch);
+    if (!(in.limit >= 0.0)) return set_error(MHPPO_EINVAL, "adam_clip_gated: net %d: limit must be >= 0 (inf allowed)", k);
+    gs.g[k] = {in.kl, in.limit, in.stop, in.epoch};
+  }
+  hipLaunchKernelGGL(k_adam_clip_gated, dim3(n_nets), dim3(NT), 0, (hipStream_t)stream, args, max_norm, norms, gs);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }

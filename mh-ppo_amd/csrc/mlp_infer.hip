@@ -1,8 +1,10 @@
 // mlp_infer.hip — forward-only kernels of a Model_PPO head outside the rollout (+ C-ABI):
 //   k_mlp_forward  one net over [M, n_in] rows, per-row output (Model_PPO.forward_rows);
 //   k_ppo_diag     actor and critic of one head over its batch, float64 sums of the per-row PPO
-//                  diagnostics (approximate KL, clip fraction, entropy, explained variance).
-// Both run 32-row tiles on f32 MFMA in the rollout's arithmetic (mlp_infer_tile.h): a wave stages
+//                  diagnostics (approximate KL, clip fraction, entropy, explained variance);
+//   k_ppo_kl       the actor alone over the same batch: the two KL sums of the diagnostics, bit for
+//                  bit, cheap enough for every epoch (the KL early stop's measurement).
+// All run 32-row tiles on f32 MFMA in the rollout's arithmetic (mlp_infer_tile.h): a wave stages
 // its tile's rows through LDS with coalesced loads, the nets' permuted weight images are staged
 // once per block, and a block walks its tiles in a fixed order (grid-stride), so the sums depend
 // only on M.  The per-row terms are the host+device functions of mlp_infer_terms.h; the block
@@ -147,6 +149,81 @@ __global__ void __launch_bounds__(ITPB) __attribute__((amdgpu_waves_per_eu(2)))
   }
 }
 
+// The actor half of k_ppo_diag alone, for the KL early stop's per-epoch measurement: one weight
+// image, one tile_forward, the two float64 sums DSUM and K3; `ret` is not read.  The grid
+// (n_blocks(M)), the tile-to-wave walk, the rows' terms (actor_row), the per-wave shuffle tree, the
+// wave order and the fold are k_ppo_diag's, so the two sums carry the diagnostics' bits.
+// LDS: [actor image][IWAVES input tiles][MHPPO_KL_N x IWAVES doubles]
+// partials: [MHPPO_KL_N][gridDim.x]
+// Registers (gfx950): 106 VGPRs at kind 1, 119 at kind 2, no AGPRs, no scratch, no VGPR spill (kind 2
+// parks 2 SGPRs in VGPR lanes), both under the 128 of four waves per SIMD, which is the bound asked
+// for: left free, the compiler puts the accumulators in AGPRs and lands at three waves; bound for
+// five it goes to scratch.  What bounds the occupancy per head width is in DESIGN.md ("KL early
+// stopping": the grid's cap of 512 blocks comes first).
+constexpr int MHPPO_KL_N = 2;
+template <int KIND>
+__global__ void __launch_bounds__(ITPB) __attribute__((amdgpu_waves_per_eu(4)))
+    k_ppo_kl(NetArg actor, int n_in, const float *__restrict__ X, int64_t M, const void *act,
+             const float *__restrict__ logp_old, double *__restrict__ partials) {
+  constexpr int NA = KIND == 2 ? 2 : 1;
+  static_assert(MHPPO_DIAG_DSUM == 0 && MHPPO_DIAG_K3 == 1, "the KL launch keeps the first two diagnostics terms");
+  extern __shared__ float lds[];
+  const int tid = threadIdx.x, l = tid & 63, j = l & 31, kh = l >> 5, w = tid >> 6;
+  const Img ga = img_layout(n_in, NA);
+  float *La = lds;
+  float *xs = La + ga.size + w * xtile_floats(ga);
+  double *wsum = reinterpret_cast<double *>(La + ga.size + IWAVES * xtile_floats(ga));
+  stage_image<ITPB>(La, ga, actor.W, n_in, NA, tid);
+  zero_x_pad(xs, ga, n_in, l);
+  const XStage xst = xstage_init(n_in, l);
+  double acc[MHPPO_KL_N] = {0.0, 0.0};
+  const int64_t ntiles = (M + 31) / 32, stride = (int64_t)gridDim.x * IWAVES;
+  for (int64_t t0 = (int64_t)blockIdx.x * IWAVES; t0 < ntiles; t0 += stride) {
+    const int64_t tile = t0 + w;
+    const bool live = tile < ntiles;
+    const int64_t r0 = tile * 32;
+    const int nr = !live ? 0 : (M - r0 < 32 ? (int)(M - r0) : 32);
+    if (live) stage_x(xs, ga, xst, X, r0, nr, n_in, l);
+    __syncthreads();
+    if (live) {
+      const bool mine = kh == 0 && j < nr;
+      const int64_t r = r0 + j;
+      // the row's scalars, issued ahead of the forward
+      float act_f = 0.0f, lp_old = 0.0f;
+      int act_i = 0;
+      if (mine) {
+        if (KIND == 2) act_i = static_cast<const int32_t *>(act)[r];
+        else act_f = static_cast<const float *>(act)[r];
+        lp_old = logp_old[r];
+      }
+      float za[NA];
+      tile_forward<NA>(La, ga, xs, j, kh, za);
+      if (mine) {
+        double t[MHPPO_DIAG_ENT + 1];
+        actor_row(KIND, za, actor.mean, actor.std, act_f, act_i, lp_old, t, nullptr);
+#pragma unroll
+        for (int k = 0; k < MHPPO_KL_N; k++) acc[k] += t[k];
+      }
+    }
+    __syncthreads();
+  }
+  // block partial in k_ppo_diag's order: a shuffle tree per wave, then the waves in index order
+#pragma unroll
+  for (int k = 0; k < MHPPO_KL_N; k++) {
+    double v = acc[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (l == 0) wsum[k * IWAVES + w] = v;
+  }
+  __syncthreads();
+  if (tid < MHPPO_KL_N) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < IWAVES; q++) s += wsum[tid * IWAVES + q];
+    partials[(size_t)tid * gridDim.x + blockIdx.x] = s;
+  }
+}
+
 // sums[k] = the fold of term k's block partials (one chain per thread, then the tree), written
 constexpr auto k_diag_fold = k_fold<ITPB, 1, false>;
 
@@ -231,6 +308,41 @@ int mhppo_ppo_diag(const mhppo_mlp *actor, const mhppo_mlp *critic, const float 
                        part);
   }
   hipLaunchKernelGGL(k_diag_fold, dim3(MHPPO_DIAG_N), dim3(ITPB), 0, s, part, nb, sums);
+  CHECK_HIP(hipGetLastError());
+  return MHPPO_OK;
+}
+
+int64_t mhppo_ppo_kl_work_bytes(int64_t M) {
+  if (M <= 0) return 8;
+  return (int64_t)MHPPO_KL_N * n_blocks(M) * (int64_t)sizeof(double);
+}
+
+int mhppo_ppo_kl(const mhppo_mlp *actor, const float *X, int64_t M, const void *act, const float *logp_old,
+                 double *sums, void *work, void *stream) {
+  if (int rc = check_net(actor, "mhppo_ppo_kl actor")) return rc;
+  if (actor->kind == 0) return set_error(MHPPO_EINVAL, "mhppo_ppo_kl: the actor is kind 0 (a critic)");
+  if (M < 0) return set_error(MHPPO_EINVAL, "mhppo_ppo_kl: M < 0");
+  if (!sums) return set_error(MHPPO_EINVAL, "mhppo_ppo_kl: null pointer (sums)");
+  hipStream_t s = (hipStream_t)stream;
+  if (M == 0) {
+    CHECK_HIP(hipMemsetAsync(sums, 0, MHPPO_KL_N * sizeof(double), s));
+    return MHPPO_OK;
+  }
+  if (!X || !act || !logp_old || !work) return set_error(MHPPO_EINVAL, "mhppo_ppo_kl: null pointer");
+  const NetArg a{actor->packed, actor->mean, actor->std};
+  const Img ga = img_layout(actor->n_in, actor->n_out);
+  const size_t shm = ((size_t)ga.size + (size_t)IWAVES * xtile_floats(ga)) * sizeof(float) +
+                     (size_t)MHPPO_KL_N * IWAVES * sizeof(double);
+  const int nb = n_blocks(M);
+  double *part = static_cast<double *>(work);
+  if (actor->kind == 2) {
+    if (int rc = allow_lds<k_ppo_kl<2>>(shm)) return rc;
+    hipLaunchKernelGGL(k_ppo_kl<2>, dim3(nb), dim3(ITPB), shm, s, a, (int)actor->n_in, X, M, act, logp_old, part);
+  } else {
+    if (int rc = allow_lds<k_ppo_kl<1>>(shm)) return rc;
+    hipLaunchKernelGGL(k_ppo_kl<1>, dim3(nb), dim3(ITPB), shm, s, a, (int)actor->n_in, X, M, act, logp_old, part);
+  }
+  hipLaunchKernelGGL(k_diag_fold, dim3(MHPPO_KL_N), dim3(ITPB), 0, s, part, nb, sums);
   CHECK_HIP(hipGetLastError());
   return MHPPO_OK;
 }

@@ -44,11 +44,14 @@ MHPPO_HD inline void critic_terms(float ret, float V, double *t) {
   t[MHPPO_DIAG_V] = v;
 }
 
-// One row of the diagnostics from the nets' raw outputs: za[] the actor's pre-finish outputs
-// (1 for kind 1, 2 for kind 2), vc the critic's output.  act: the row's action (kind 1: the float
-// action; kind 2: 0 / 1).  Returns d; *lp_new (optional) = logp_new.
-MHPPO_HD inline double diag_row(int kind, const float *za, float mean, float std, float vc, float act_f, int act_i,
-                                float logp_old, float ret, double *t, float *lp_new) {
+// The actor half of one row from the actor's raw outputs: the head's finish, logp_new, then
+// actor_terms (t entries DSUM .. ENT written).  za[] the pre-finish outputs (1 for kind 1, 2 for
+// kind 2), act the row's action (kind 1: the float action; kind 2: 0 / 1).  Returns d; *lp_new
+// (optional) = logp_new.  The one copy both k_ppo_diag and k_ppo_kl run: the KL launch's two sums
+// are the diagnostics' DSUM and K3 terms, row for row (a caller that reads only those leaves the
+// clip, ratio and entropy terms to the compiler's dead-code elimination).
+MHPPO_HD inline double actor_row(int kind, const float *za, float mean, float std, float act_f, int act_i,
+                                 float logp_old, double *t, float *lp_new) {
   float lp;
   double ent = 0.0;
   if (kind == 2) {
@@ -63,8 +66,15 @@ MHPPO_HD inline double diag_row(int kind, const float *za, float mean, float std
     lp = mvn_logp(act_f, finish_cont<LibmRollout>(za[0], mean, std));
   }
   if (lp_new) *lp_new = lp;
-  critic_terms(ret, vc, t);
   return actor_terms(lp, logp_old, ent, t);
+}
+
+// One row of the diagnostics from the nets' raw outputs: actor_row's arguments, vc the critic's
+// output.  Returns d; *lp_new (optional) = logp_new.
+MHPPO_HD inline double diag_row(int kind, const float *za, float mean, float std, float vc, float act_f, int act_i,
+                                float logp_old, float ret, double *t, float *lp_new) {
+  critic_terms(ret, vc, t);
+  return actor_row(kind, za, mean, std, act_f, act_i, logp_old, t, lp_new);
 }
 
 }  // namespace infer

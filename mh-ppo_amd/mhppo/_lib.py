@@ -64,6 +64,10 @@ class AdamNet(ctypes.Structure):  # mhppo_adam_net
                 ("bias2", F64), ("beta1", F64), ("beta2", F64), ("eps", F64)]
 
 
+class AdamGate(ctypes.Structure):  # mhppo_adam_gate
+    _fields_ = [("kl", P), ("limit", F64), ("stop", P), ("epoch", I32), ("reserved", I32)]
+
+
 # name: (restype, argtypes)
 _SIGS = {
     "mhppo_env_create": (I32, [ctypes.POINTER(EnvCfg), I32, ctypes.POINTER(P)]),
@@ -122,6 +126,9 @@ _SIGS = {
     "mhppo_eval_stats_row": (I32, [P, P, I32, I32, P, P]),
     "mhppo_eval_stats_fold": (I32, [P, P, P, P]),
     "mhppo_adam_clip": (I32, [P, I32, F64, P, P]),
+    "mhppo_adam_clip_gated": (I32, [P, I32, F64, P, P, P]),
+    "mhppo_ppo_kl_work_bytes": (I64, [I64]),
+    "mhppo_ppo_kl": (I32, [ctypes.POINTER(Mlp), P, I64, P, P, P, P, P]),
     "mhppo_batch_shuffle": (I32, [I32, I64, P, P, P, P, U64, I32, P, P, P, P, P, P]),
     "mhppo_policy_dims": (I32, [ctypes.POINTER(EnvCfg), P]),
     "mhppo_policy_decide": (I32, [ctypes.POINTER(EnvCfg), ctypes.POINTER(Mlp), P, I64, P, P, P]),
@@ -235,6 +242,21 @@ def adam_clip(nets, n_nets, max_norm, norms, stream):
     with max_grad_norm set), so a run with the knob off can be shown never to reach it.  `nets`: a
     ctypes array of AdamNet (host), `norms` / `stream`: addresses."""
     return check(lib().mhppo_adam_clip(ctypes.addressof(nets), n_nets, max_norm, norms, stream))
+
+
+def adam_clip_gated(nets, n_nets, max_norm, norms, gates, stream):
+    """mhppo_adam_clip_gated, checked: the one place the entry point is called from
+    (mhppo.adam.adam_clip_steps with gates: the KL early stop), so a run with target_kl off can be
+    shown never to reach it.  `nets` / `gates`: ctypes arrays of AdamNet / AdamGate (host; gates
+    may be None), `norms` / `stream`: addresses."""
+    return check(lib().mhppo_adam_clip_gated(ctypes.addressof(nets), n_nets, max_norm, norms,
+                                             None if gates is None else ctypes.addressof(gates), stream))
+
+
+def ppo_kl(actor, X, M, act, logp_old, sums, work, stream):
+    """mhppo_ppo_kl, checked: the one place the entry point is called from (mhppo.ppo.k_ppo_kl and
+    train_epochs' KL launches).  `actor`: an Mlp (by reference); the rest addresses (or None)."""
+    return check(lib().mhppo_ppo_kl(ctypes.byref(actor), X, M, act, logp_old, sums, work, stream))
 
 
 def batch_shuffle(n_in, M, X, act, logp, ret, key, K, X_out, act_out, logp_out, ret_out, counts, stream):

@@ -56,10 +56,10 @@ def _group_keys(opts):
 _ADAM_PLANS = {}
 
 
-def adam_steps(opts, max_grad_norm=None, norms_out=None):
+def adam_steps(opts, max_grad_norm=None, norms_out=None, gates=None):
     """One step of every optimiser in `opts`.  max_grad_norm set (opt-in): every net's gradient is
     clipped to that norm first and the step runs on the native clip-and-Adam launch
-    (adam_clip_steps below; norms_out as there); the rest of this text is the default, None.
+    (adam_clip_steps below; norms_out and gates as there); the rest of this text is the default, None.
 
     Bit-identical to calling o.step() on each.  For
     fused torch Adams (the GPU path) whose state exists, the steps of all six nets run as ONE
@@ -74,7 +74,9 @@ def adam_steps(opts, max_grad_norm=None, norms_out=None):
     reused (_AdamPlan: ~0.2 ms of host time per call otherwise).  Pinned by
     test_adam_steps_bit_identical_to_per_optimizer_steps."""
     if max_grad_norm is not None:
-        return adam_clip_steps(opts, max_grad_norm, norms_out)
+        return adam_clip_steps(opts, max_grad_norm, norms_out, gates)
+    if gates is not None:
+        raise ValueError("gates need the native launch: pass max_grad_norm (inf clips nothing)")
     key = tuple(id(o) for o in opts)
     plan = _ADAM_PLANS.get(key)
     if plan is not None and plan.opts == list(opts) and plan.valid(opts):
@@ -291,6 +293,13 @@ def _clip_net(o):
     return rec
 
 
+def clip_prepare(opts):
+    """Build the clip path's records of `opts` now (one host read of the step count per optimiser
+    whose record is missing or stale), so that the steps that follow find them and read nothing."""
+    for o in opts:
+        _clip_net(o)
+
+
 def _clip_table(recs):
     nets = (_lib.AdamNet * len(recs))()
     for net, rec in zip(nets, recs):
@@ -301,20 +310,36 @@ def _clip_table(recs):
     return nets
 
 
-def _clip_launch(recs, nets, max_norm, norms):
-    """One mhppo_adam_clip call for `recs` (all on one GPU) on the current stream."""
+def _clip_launch(recs, nets, max_norm, norms, gates=None):
+    """One mhppo_adam_clip call for `recs` (all on one GPU) on the current stream; with `gates` (a
+    ctypes array of _lib.AdamGate, one per record) one mhppo_adam_clip_gated call instead."""
     hs = [rec.hyper() for rec in recs]
     for net, (t, lr, b1, b2, eps) in zip(nets, hs):
         net.t, net.alpha, net.bias2 = t, lr / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t)
         net.beta1, net.beta2, net.eps = b1, b2, eps
     dev = recs[0].dev
     with (contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)):
-        _lib.adam_clip(nets, len(recs), max_norm, norms.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if gates is None:
+            _lib.adam_clip(nets, len(recs), max_norm, norms.data_ptr(), st)
+        else:
+            _lib.adam_clip_gated(nets, len(recs), max_norm, norms.data_ptr(), gates, st)
     for rec in recs:
         rec.t += 1
 
 
-def adam_clip_steps(opts, max_grad_norm, norms_out=None):
+def gate_table(entries):
+    """The host array of mhppo_adam_gate for one gated call: per optimiser None (not gated) or
+    (kl address, limit, stop address, epoch): kl the device address of the net's two float64 KL
+    sums, stop of its int32 stop word (include/mhppo.h)."""
+    tab = (_lib.AdamGate * max(1, len(entries)))()
+    for g, e in zip(tab, entries):
+        if e is not None:
+            g.kl, g.limit, g.stop, g.epoch = e[0], float(e[1]), e[2], int(e[3])
+    return tab
+
+
+def adam_clip_steps(opts, max_grad_norm, norms_out=None, gates=None):
     """adam_steps with the knob set: per optimiser (= per net) clip the gradient to max_grad_norm
     (> 0; inf clips nothing and only measures), then one Adam step.  Returns the float64 norms
     before clipping, one per optimiser in order, in norms_out (float64, contiguous,
@@ -333,7 +358,12 @@ def adam_clip_steps(opts, max_grad_norm, norms_out=None):
     maximize, capturable, differentiable, a tensor lr, several param groups, more than 8 parameter
     tensors, non-float32 or non-contiguous tensors, a GPU optimiser that is not fused=True (its
     `step` lives on the host), step hooks) takes torch.nn.utils.clip_grad_norm_ on its
-    parameters, then o.step(); the others of the call still go native, one launch each."""
+    parameters, then o.step(); the others of the call still go native, one launch each.
+    gates (opt-in, the KL early stop: gate_table's array, one entry per optimiser): the one launch
+    is mhppo_adam_clip_gated, and a net whose gate is closed on the device takes no step (its norm
+    is NaN, its state keeps its bits).  The host-side step count of its record is then one ahead
+    of the state's `step`: the caller drops the records (clip_forget) before that optimiser's next
+    step.  Gates are served by the all-native launch alone: a CPU or unsupported optimiser raises."""
     max_norm = float(max_grad_norm)
     if not max_norm > 0.0:
         raise ValueError(f"max_grad_norm must be > 0 (inf allowed), not {max_grad_norm!r}")
@@ -358,8 +388,11 @@ def adam_clip_steps(opts, max_grad_norm, norms_out=None):
             if len(_CLIP_PLANS) > 64:
                 _CLIP_PLANS.clear()
             _CLIP_PLANS[key] = (recs, nets)
-        _clip_launch(recs, nets, max_norm, norms_out)
+        _clip_launch(recs, nets, max_norm, norms_out, gates)
         return norms_out
+    if gates is not None:
+        raise ValueError("a gated step needs fused torch.optim.Adam optimisers on one GPU (the gate is decided "
+                         "on the device: there is no CPU path)")
     for k, (o, rec) in enumerate(zip(opts, recs)):
         if rec.ok and rec.dev.type == "cuda":
             one = norms_out[k:k + 1] if norms_out.device == rec.dev else torch.empty(1, dtype=torch.float64,

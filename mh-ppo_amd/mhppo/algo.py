@@ -224,7 +224,15 @@ class Algo_PPO:
         self.grad_norms = []
         self._pending_norms = []  # (pinned [10, 2H] norms, event, iteration, head names)
         self._norms_dev = None    # update()'s (norms tensor, head names) of the current iteration
-        self._external = None     # train_external's (its arguments' key, ExternalRollout): its buffers are allocated once
+        # Opt-in KL early stop (Algo_PPO(target_kl=tau)): one entry per iteration,
+        # {"iteration": i, "cross": {"actor_steps": s, "approx_kl": [KL_1 .. KL_9]}, ...} for the heads
+        # trained that iteration: s the actor's Adam steps (10 when it never stopped), KL_e the
+        # approximate KL of the actor after e steps (after a stop the values repeat).  They land like
+        # the gradient norms.  Not checkpointed: a resumed run starts empty.
+        self.kl_stops = []
+        self._pending_kl = []     # (pinned [9 H 2 + H] doubles, event, iteration, head names, row counts)
+        self._kl_dev = None       # update()'s (kl, stop, head names, row counts) of the current iteration
+        self._external = None    # train_external's (its arguments' key, ExternalRollout): its buffers are allocated once
 
     def nets(self):
         return [self.actor_net_cross, self.actor_net_wait, self.actor_net_choice, self.critic_net_cross,
@@ -281,8 +289,27 @@ class Algo_PPO:
         # gae_lambda is.  Under data parallelism every rank shuffles its own shard: a different draw
         # of minibatches than one process on all envs.
         self.minibatches = None
+        # KL early stopping (beyond the reference, whose ten epochs per head are unconditional; the
+        # target_kl of Spinning Up, SB3, CleanRL and RLlib): None = off, update() makes exactly the
+        # calls it always did; a float tau > 0 measures, before each actor step but the first, the
+        # approximate KL of the head's current policy from the one that collected the batch
+        # (mhppo.ppo.k_ppo_kl: the diagnostics' approx_kl over the whole batch) and stops that head's
+        # ACTOR for the rest of the iteration once it exceeds 1.5 tau; the critic takes all ten steps
+        # (Spinning Up's rule).  The decision is made on the device inside the clip-and-Adam launch
+        # (mhppo.ppo.train_epochs): no host sync, and every step of the iteration then runs on the
+        # native launch, as with max_grad_norm.  A stopped actor's train passes still run (their
+        # gradient is discarded).  inf never stops and only records (self.kl_stops).  Not with
+        # minibatches.  A constructor argument, as gae_lambda is: nothing of it is checkpointed.
+        self.target_kl = None
         for k, v in hyperparameters.items():
             setattr(self, k, v)
+        if self.target_kl is not None:
+            tau = float(self.target_kl)
+            if not tau > 0.0:  # (NaN fails the comparison)
+                raise ValueError(f"target_kl must be None or a float > 0 (inf allowed), not {self.target_kl!r}")
+            if self.minibatches is not None:
+                raise ValueError("target_kl does not combine with minibatches: the gate is per full-batch epoch")
+            self.target_kl = tau
         if self.max_grad_norm is not None:
             c = float(self.max_grad_norm)
             if not c > 0.0:  # (NaN fails the comparison)
@@ -347,8 +374,15 @@ class Algo_PPO:
                                           per_row=kind == "d" and self.fix_choice_loss, exact=self.exact_f32))
                     names.append(name)
             clip = getattr(self, "max_grad_norm", None)
+            tau = getattr(self, "target_kl", None)
             if K is not None:
                 losses = self._update_minibatches(heads, names, K, clip, slice_m) if heads else None
+            elif tau is not None:
+                losses = None
+                if heads:
+                    losses, norms, kl, stop = ppo.train_epochs(heads, 10, self.grad_bucket, clip, tau)
+                    self._norms_dev = None if norms is None else (norms, names)
+                    self._kl_dev = (kl, stop, names, [h.m for h in heads])
             elif clip is None:
                 losses = ppo.train_epochs(heads, 10, self.grad_bucket) if heads else None
             else:
@@ -494,6 +528,8 @@ class Algo_PPO:
             self._queue_diagnostics()
         if getattr(self, "_norms_dev", None) is not None:
             self._queue_grad_norms()
+        if getattr(self, "_kl_dev", None) is not None:
+            self._queue_kl_stops()
         # the reward curves' sums over (cross, wait, choice): from the bucketing pass on the GPU
         # (bucket_segments: fixed-order float64 partials), else torch reductions
         sums = (self.rollout.choice or {}).get("rew_sums")
@@ -528,10 +564,10 @@ class Algo_PPO:
             print("Complete")
 
     def _land_pending(self, keep_last=False):
-        """Land the queued read-backs of the reward curves, the gradient norms and the diagnostics
-        (keep_last: all but each queue's newest entry).  A queue an object lacks is empty."""
+        """Land the queued read-backs of the reward curves, the gradient norms, the KL stops and the
+        diagnostics (keep_last: all but each queue's newest entry).  A queue an object lacks is empty."""
         for name, append in (("_pending_curves", self._append_curves), ("_pending_norms", self._append_grad_norms),
-                             ("_pending_diag", self._append_diagnostics)):
+                             ("_pending_kl", self._append_kl_stops), ("_pending_diag", self._append_diagnostics)):
             _land(getattr(self, name, []), append, keep_last)
 
     def _flush_curves(self):
@@ -591,9 +627,30 @@ class Algo_PPO:
                 entry[f"{kind}_{name}"] = cols[off + j]
         self.grad_norms.append(entry)
 
+    def _queue_kl_stops(self):
+        """The iteration's KL sums and stop words (update()'s device tensors) on their way to the
+        host in one copy, appended by _append_kl_stops once they have landed.  The sums are global
+        and the stops replicated: equal on every rank, no collective."""
+        kl, stop, names, ms = self._kl_dev
+        self._kl_dev = None
+        both = torch.cat([kl.reshape(-1), stop.to(torch.float64)])
+        self._pending_kl.append(_readback(both, int(self.total_loop), list(names), list(ms)))
+
+    def _append_kl_stops(self, host, it, names, ms):
+        """One kl_stops entry from train_epochs' kl [E - 1, H, 2] and stop [H] (flattened, the stops last)."""
+        H = len(names)
+        flat = host.tolist()
+        kl, stop = flat[:len(flat) - H], flat[len(flat) - H:]
+        E1 = len(kl) // (2 * H)
+        entry = {"iteration": it}
+        for i, (name, m) in enumerate(zip(names, ms)):
+            entry[name] = {"actor_steps": int(stop[i]) or E1 + 1,
+                           "approx_kl": [kl[(e * H + i) * 2 + 1] / m for e in range(E1)]}
+        self.kl_stops.append(entry)
+
     def curves(self):
         """The reward curves with every pending entry appended: (cross, wait, choice, balance).
-        (Also lands every pending entry of self.diagnostics and self.grad_norms.)"""
+        (Also lands every pending entry of self.diagnostics, self.grad_norms and self.kl_stops.)"""
         self._land_pending()
         return self.ep_reward_cross, self.ep_reward_wait, self.ep_reward_choice, self.ep_scenario_balance
 

@@ -35,7 +35,8 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .adam import adam_clip_steps, adam_clip_sumsq, adam_clip_torch, adam_steps, clip_forget, fold_1024_4  # noqa: F401
+from .adam import (adam_clip_steps, adam_clip_sumsq, adam_clip_torch, adam_steps, clip_forget, fold_1024_4,  # noqa: F401
+                   clip_prepare, gate_table)
 
 
 _FORCE_COLLECTIVES = False
@@ -353,6 +354,65 @@ def k_ppo_diag(head):
     return sums
 
 
+def _kl_args(head):
+    """(actor's mhppo_mlp, its backing tensor, obs, act, logp, M) of a Head as mhppo_ppo_kl reads them."""
+    actor = head.actor
+    want = 1 if head.kind == "c" else 2
+    if actor.model_type != want:
+        raise ValueError(f"a kind {head.kind!r} head has a model_type {want} actor")
+    dev = head.obs.device
+    if dev.type != "cuda":
+        raise ValueError(f"the KL pass runs on the GPU only (there is no CPU path), not on {dev}")
+    obs = head.obs.float().contiguous()
+    act = head.act.float().contiguous() if head.kind == "c" else head.act.to(torch.int32).contiguous()
+    da, keep = actor.mlp_desc()
+    return da, keep, obs, act, head.logp.float().contiguous(), obs.shape[0]
+
+
+def _kl_work(head, M, dev):
+    need = max(1, (int(_lib.lib().mhppo_ppo_kl_work_bytes(M)) + 7) // 8)
+    work = getattr(head, "_kl_work", None)
+    if work is None or work.numel() < need or work.device != dev:
+        work = head._kl_work = torch.empty(need, dtype=torch.float64, device=dev)
+    return work
+
+
+def k_ppo_kl(head, out=None):
+    """This rank's float64 [2] KL sums of one Head (mhppo_ppo_kl): (sum d, sum (expm1(d) - d)),
+    d = logp_new - logp_old, from the actor's forward over head.obs with its current weights --
+    bit for bit k_ppo_diag(head)[:2], with neither the critic nor `ret` read.  Forward only, one
+    launch plus the fold, on the current stream; nothing is synchronised.  out: a contiguous
+    float64 [2] device tensor to write (default: a new one).  The scratch is allocated once per head
+    (head._kl_work) and reused.  Not a train pass: it does not enter TRAIN_EVENTS."""
+    da, keep, obs, act, logp, M = _kl_args(head)
+    dev = obs.device
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous float64 [2] tensor on the head's device")
+    work = _kl_work(head, M, dev)
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        _lib.ppo_kl(da, p(obs), M, p(act), p(logp), p(out), p(work), _lib.stream_ptr())
+    return out
+
+
+# The KL early stop's rule (Algo_PPO(target_kl=tau), train_epochs), as the gated Adam launch applies
+# it on the device (include/mhppo.h mhppo_adam_clip_gated): its executable specification.
+def kl_limit(target_kl, m):
+    """The gate's bound on a head's GLOBAL K3 sum: 1.5 * target_kl * m (float64; m the global row
+    count).  In sum units, so the kernel never divides: mean KL <= 1.5 tau  <=>  sum <= limit."""
+    return 1.5 * float(target_kl) * float(m)
+
+
+def kl_gate(kl_sum, limit, stop, epoch):
+    """One gated net at one step: (open, stop').  open iff the net has not stopped (stop == 0) and
+    kl_sum <= limit (a NaN fails the comparison and closes); the call that first closes the net
+    records its epoch, and a stop is sticky.  A pure function."""
+    is_open = stop == 0 and kl_sum <= limit
+    return is_open, (stop if (is_open or stop != 0) else int(epoch))
+
+
 def diag_stats(sums, m, entropy=True):
     """The per-iteration diagnostics of one head from its GLOBAL sums (a sequence of DIAG_N floats:
     all ranks' k_ppo_diag sums added) and global row count m.  A pure function.
@@ -465,18 +525,21 @@ def _on_device(dev):
     return torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()
 
 
-def _reduce_and_step(nets, opts, bucket, max_grad_norm, norms_out):
+def _reduce_and_step(nets, opts, bucket, max_grad_norm, norms_out, gates=None):
     """A step's epilogue: the gradient all-reduce of `nets` (in the bucket, or packed), then one
     adam_steps call over `opts`, their optimisers in the driver's order, clipped when max_grad_norm
-    is set (norms_out: float64, contiguous, one element per optimiser, or None)."""
+    is set (norms_out: float64, contiguous, one element per optimiser, or None; gates: the KL early
+    stop's gate table of the step, adam.gate_table)."""
     if bucket is not None:
         bucket.allreduce(nets)
     else:
         _allreduce_net_grads(*nets)
     if max_grad_norm is None:
         adam_steps(opts)
-    elif opts:
+    elif opts and gates is None:
         adam_steps(opts, max_grad_norm, norms_out)
+    elif opts:
+        adam_steps(opts, max_grad_norm, norms_out, gates)
 
 
 def train_epoch(heads, bucket=None, max_grad_norm=None, norms_out=None):
@@ -526,7 +589,21 @@ def _side_streams(dev, n):
     return _SIDE_STREAMS[key]
 
 
-def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None):
+class _KLPlan:
+    """One head's mhppo_ppo_kl arguments for a whole gated train_epochs call, resolved once (the
+    actor's descriptor points at its live flat weights, which Adam updates in place)."""
+
+    def __init__(self, h):
+        self.desc, *self.keep, self.M = _kl_args(h)
+        obs, act, lp = self.keep[1:]
+        self.keep.append(_kl_work(h, self.M, obs.device))
+        self.x, self.a, self.l, self.w = (_lib.ptr(t) for t in (obs, act, lp, self.keep[-1]))
+
+    def launch(self, out, st):
+        _lib.ppo_kl(self.desc, self.x, self.M, self.a, self.l, out.data_ptr(), self.w, st)
+
+
+def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None, target_kl=None):
     """n_epochs full-batch epochs of every head, run as a pipeline of n_epochs + 1 steps: step k
     runs the actor passes of epoch k - 1 and the critic passes of epoch k (a continuous head on the
     split-precision kernel: ONE fused launch, mhppo_mlp_train_pair), then one gradient all-reduce
@@ -546,13 +623,50 @@ def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None):
     on the device, norms[e, j] the norm before clipping of head j's critic at its epoch e,
     norms[e, H + j] of head j's actor; NaN where a net was not stepped.  The launches fill it in
     place, without a host read: step k's nets are (actors of epoch k - 1, critics of epoch k),
-    which in this layout are 2 H consecutive doubles starting at row k - 1, column H."""
+    which in this layout are 2 H consecutive doubles starting at row k - 1, column H.
+    target_kl (opt-in, the KL early stop; None: not a line of the above changes): a float tau > 0
+    (inf measures and never stops).  Spinning Up's rule: the policy stops, the value function does
+    not.  With theta_e the actor after e Adam steps and KL_e = (1 / m) sum (expm1(d) - d) over the
+    head's whole batch under theta_e, the actor's step e (e = 1 .. n_epochs - 1; step 0 is never
+    gated) is taken iff the head has not stopped and KL_e <= 1.5 tau (kl_gate; NaN stops); a stop
+    is sticky for the rest of the call; the critics take all their steps.  So a head that stops
+    at e has the actor of an e-epoch update and the critic of the full one.  Schedule: pipeline
+    step k >= 2 first launches mhppo_ppo_kl per head (on the head's stream, after step k - 1's
+    Adam) into kl[k - 2]; under data parallelism kl[k - 2] rides in the step's advantage-sum
+    all-reduce (still two collectives per step; the last step, which has no critic pass, reduces it
+    alone), so every rank decides alike; the step's one Adam launch is mhppo_adam_clip_gated with the
+    actors gated by (kl[k - 2, i], kl_limit(tau, m_i), stop[i], epoch k - 1) and the critics
+    ungated, max_norm inf when max_grad_norm is None.  The gate is decided on the device: nothing is
+    read back, there is no host synchronisation between the loop's first and last launch.  Every
+    step then runs on the native launch, which differs from torch._fused_adam_ by the rounding of
+    the two bias corrections (include/mhppo.h).  The train passes of a stopped actor still run and
+    their gradient is discarded: skipping them needs a host decision or an exit in the train
+    kernel.  Returns (losses, norms, kl, stop): norms as above, or None when max_grad_norm is
+    None; kl float64 [n_epochs - 1, H, 2] on the device, the GLOBAL (sum d, sum (expm1(d) - d)) of
+    theta_e in kl[e - 1, i] (after a head's stop its rows repeat: the actor no longer moves);
+    stop int32 [H], the actor steps taken when head i stopped (1 .. n_epochs - 1), 0 if it never did.
+    Step counts: the clip records of the actors' optimisers are built before the loop (one host
+    read each where missing) and dropped after it (clip_forget): a closed gate takes no step, so
+    the host-side count runs ahead of the state's `step` tensor, which stays the truth."""
     H = len(heads)
     dev = heads[0].obs.device
+    gated = target_kl is not None
+    if gated:
+        tau = float(target_kl)
+        if not tau > 0.0:  # (NaN fails the comparison)
+            raise ValueError(f"target_kl must be None or a float > 0 (inf allowed), not {target_kl!r}")
+        if any(h.obs.device.type != "cuda" for h in heads):
+            raise ValueError("target_kl needs every head on a GPU: the KL pass and the gate have no CPU path")
     with _on_device(dev):
         norms = None
-        if max_grad_norm is not None:
+        if max_grad_norm is not None or gated:
             norms = torch.full((n_epochs, 2 * H), math.nan, dtype=torch.float64, device=dev)
+        if gated:
+            kl = torch.zeros(max(0, n_epochs - 1), H, 2, dtype=torch.float64, device=dev)
+            stop = torch.zeros(H, dtype=torch.int32, device=dev)
+            klp = [_KLPlan(h) for h in heads]
+            limits = [kl_limit(tau, h.m) for h in heads]
+            clip_prepare([h.opt_actor for h in heads])
         all_sums = torch.zeros(n_epochs + 1, 2 * H, 3, dtype=torch.float64, device=dev)
         dp = _dp()
         plans = [_HeadPlan(h) for h in heads]
@@ -579,6 +693,8 @@ def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None):
                 st = handles[j]
                 # (one stream: main is the current stream already; the launch events record on it)
                 with (torch.cuda.stream(streams[j]) if side else same_stream):
+                    if gated and k >= 2:  # KL of the actor after its k - 1 steps, ahead of its pass
+                        klp[i].launch(kl[k - 2, i], st)
                     stp = None
                     if k > 0:  # the previous step's critic pass sums (all-reduced under data parallelism)
                         stp = stats[2 * i:2 * i + 2] if dp else all_sums[k - 1, i, 1:3]
@@ -597,16 +713,36 @@ def train_epochs(heads, n_epochs, bucket=None, max_grad_norm=None):
                     out[i][1] = sums[i, 0:1]
             for sd in side:  # join
                 main.wait_stream(sd)
-            if crit and dp:  # the all-reduce needs one span
+            klk = kl[k - 2] if gated and k >= 2 else None
+            if crit and dp and klk is not None:  # the KL sums ride with the advantage sums: one collective
+                buf = torch.cat([sums[:H, 1:3].reshape(-1), klk.reshape(-1)])
+                _allreduce_(buf)
+                stats = buf[:2 * H]
+                klk.copy_(buf[2 * H:].view(H, 2))
+            elif crit and dp:  # the all-reduce needs one span
                 stats = sums[:H, 1:3].reshape(-1).contiguous()
                 _allreduce_(stats)
+            elif dp and klk is not None:  # the last step: no critic pass, the KL sums alone
+                _allreduce_(klk)
             # all H actors (k > 0), then all H critics (k < n_epochs)
             opts = ([h.opt_actor for h in heads] if k > 0 else []) + ([h.opt_critic for h in heads] if crit else [])
             nout = None
             if norms is not None:
                 off = (k - 1) * 2 * H + H if k > 0 else 0
                 nout = norms.view(-1)[off:off + len(opts)]
-            _reduce_and_step(trained, opts, bucket, max_grad_norm, nout)
+            if not gated:
+                _reduce_and_step(trained, opts, bucket, max_grad_norm, nout)
+                continue
+            # the actors of step k >= 2 are gated by the KL of their k - 1 steps; step 0 (k == 1) and the critics never
+            ent = [None] * len(opts)
+            if klk is not None:
+                ent[:H] = [(klk[i].data_ptr(), limits[i], stop[i].data_ptr(), k - 1) for i in range(H)]
+            _reduce_and_step(trained, opts, bucket, math.inf if max_grad_norm is None else max_grad_norm, nout,
+                             gate_table(ent))
+        if gated:
+            clip_forget([h.opt_actor for h in heads])
+    if gated:
+        return [tuple(o) for o in out], (norms if max_grad_norm is not None else None), kl, stop
     if norms is not None:
         return [tuple(o) for o in out], norms
     return [tuple(o) for o in out]
