@@ -919,6 +919,89 @@ int mhppo_gae_tm_boot(const mhppo_mlp *critic0, const mhppo_mlp *critic1, const 
                       const int64_t *pos, const int8_t *bucket, int64_t B, int32_t T, double gamma, double lambda,
                       float *ret_tm, float *value_tm, const int32_t *len_rec, const float *v_boot, void *stream);
 
+/* ---- auto-reset of external rollouts (opt-in: ExternalRollout(auto_reset=E); the calls above keep
+ * their launches and their bits) ----
+ * A vectorised simulator resets a stream the moment it reports done: stream r plays episode after episode
+ * inside the T-step window.  Stream r owns E >= 1 LANES; lane e of stream r is the e-th episode the stream
+ * starts in the window, lane v = e M + r, lane-segment (v, i) = v S + i, E M S <= 2^31 - 1.  Lane 0 starts
+ * at step 0.  If stream r reports done at recorded step t while its current lane e runs, the lane ends
+ * with len = t + 1 - t0 (terminal: V = 0 after it).  If e + 1 < E and step t + 1 is acted on, lane e + 1
+ * starts at t0 = t + 1 with a choice decision of its own, drawn from the row handed to that step (same-step
+ * auto-reset: after a done the simulator's row is already the new episode's first).  With e + 1 == E the
+ * stream idles for the rest of the window: its records are stored, nothing of them reaches a lane.  The
+ * records keep the identity layout at wall-clock time: column r S + i of step t.
+ *
+ * mhppo_decision: one set of mhppo_policy_sample_decide outputs, for M rows or (lane-major) E M lanes:
+ * a_d int32 [., S, P], logp_d float32 [., S, P], probs float32 [., S, P, 2], feat_d float32 [., S, P, dc],
+ * closest int32 [., S], exist uint8 [., S].
+ * mhppo_lanes: the lanes' arrays.  d (lane-major decisions; exist 0 for a lane never started), ep_min
+ * float64 [E M, S], t0 int32 [E M] (0 for a lane never started), len int32 [E M] (0: open, or never
+ * started) are what the batch reads; cur int32 [2 M] is private: cur[(t & 1) M + r] is stream r's current
+ * lane at step t.  restart(t) reads half (t - 1) & 1 and writes half t & 1, so no thread of a launch reads
+ * what another writes.
+ *
+ * begin    lane 0 of every array of d <- first, every other lane 0; ep_min +0.0; t0, len, cur 0.
+ * restart  step t in [1, T), before record(t), once per step and for every step (a caller with E == 1 may
+ *          skip them all: nothing can restart).  Stream r restarts iff its current lane e is closed
+ *          (len != 0) and e + 1 < E.  For those: every array of lane e + 1 of d and of `current` (the M-row
+ *          decision mhppo_policy_sample_act reads) <- fresh's rows of stream r; t0 = t; cur = e + 1.  A
+ *          stream that does not restart keeps `current` and its lanes bit for bit.
+ * record   step t in [0, T): the step's records exactly as mhppo_record_step stores them in the identity
+ *          layout (one contiguous run per block of 256 segments), for every stream, idle or not; the current
+ *          lane's ep_min takes mhppo_record_step's minimum if the lane runs on entry; a running lane with
+ *          done[r] != 0 closes with len = t + 1 - t0.
+ * close    after k >= 1 recorded steps, into arrays of the caller's (lanes is not changed: recording may go
+ *          on): len_out[v] = k - t0[v] and cut_out[v] = 1 for a started lane still open, else len[v] and 0.
+ * Each is ONE launch; no atomics, nothing depends on the grid, no host read.  M == 0 launches nothing.
+ * MHPPO_EINVAL, nothing written: E < 1, M < 0, S < 1, E M S > 2^31 - 1; P < 1 or dc < 1 (begin, restart); t
+ * outside its range; k outside [1, T]; for M > 0 any NULL pointer. */
+typedef struct {
+  int32_t *a_d;
+  float *logp_d, *probs, *feat_d;
+  int32_t *closest;
+  uint8_t *exist;
+} mhppo_decision;
+typedef struct {
+  mhppo_decision d;
+  double *ep_min;
+  int32_t *t0, *len, *cur;
+} mhppo_lanes;
+int mhppo_lanes_begin(const mhppo_lanes *lanes, int32_t E, int64_t M, int32_t S, int32_t P, int32_t dc,
+                      const mhppo_decision *first, void *stream);
+int mhppo_lanes_restart(const mhppo_lanes *lanes, int32_t E, int64_t M, int32_t S, int32_t P, int32_t dc, int32_t t,
+                        int32_t T, const mhppo_decision *fresh, const mhppo_decision *current, void *stream);
+int mhppo_lanes_record(const mhppo_lanes *lanes, int32_t E, int64_t M, int32_t S, int32_t t, int32_t T,
+                       const float *act, const float *logp, const float *feat_c, const double *rew,
+                       const double *rew_light, float *obs_c_tm, float *act_tm, float *logp_tm, double *rew_tm,
+                       const uint8_t *done, void *stream);
+int mhppo_lanes_close(const mhppo_lanes *lanes, int32_t E, int64_t M, int32_t k, int32_t T, int32_t *len_out,
+                      uint8_t *cut_out, void *stream);
+
+/* The reward-to-go of the lanes over the wall-clock records rew float64 [T, M S] -> ret float32 [T, M S]:
+ * lane-segment q = v S + i (v = e M + r) with pos[q] >= 0 scans column r S + i over t = t0[v] + L - 1 .. t0[v]
+ * in float64, L = len[v], from G = (cut[v] && v_boot) ? (double)v_boot[r S + i] : 0, and stores float32;
+ * every record in no used lane gets ret = 0 (a memset before the launch).  pos int64 [E M S] as
+ * mhppo_bucket_plan writes it over N = E M; t0 / len int32 [E M] and cut uint8 [E M] as mhppo_lanes_close
+ * leaves them (a lane whose t0 / len leave [0, T] is clamped into it); v_boot float32 [M S] or NULL.  One
+ * thread per lane-segment, consecutive threads on consecutive columns.
+ * MHPPO_EINVAL: E < 1, M < 0, S < 1, E M S > 2^31 - 1, T < 1, for M > 0 a NULL pointer other than v_boot. */
+int mhppo_returns_scan_tm_lanes(const double *rew, float *ret, int64_t M, int32_t S, int32_t E, int32_t T,
+                                double gamma, const int64_t *pos, const int32_t *t0, const int32_t *len,
+                                const uint8_t *cut, const float *v_boot, void *stream);
+
+/* mhppo_bucket_scatter_ragged over lanes: record (t0[v] + j, r S + i) of a lane-segment q = v S + i with
+ * row0[q] >= 0 goes to row row0[q] + j of dst[bucket[q]], j < len[v]; nothing else is written.  row0 int64
+ * / bucket int8 [E M S] as mhppo_ragged_plan / mhppo_bucket_plan write them over the E M lanes.  The lanes
+ * of a stream must not overlap in time (mhppo_lanes_close's do not); the caller's buffers hold every row
+ * row0[q] + len[v] - 1.  rew_sums[b] adds (double)(float)rew over bucket b's records in the fixed order of
+ * mhppo_bucket_scatter_sums: the blocks are 64 columns x 16 steps of the records, so with E == 1 the sums
+ * are mhppo_bucket_scatter_ragged's bit for bit.  work: mhppo_bucket_work_bytes(M S, T) bytes.
+ * MHPPO_EINVAL: E < 1, M < 0, S < 1, E M S > 2^31 - 1, T < 1, dst NULL, for M > 0 any NULL pointer. */
+int mhppo_bucket_scatter_lanes(const int64_t *row0, const int8_t *bucket, const int32_t *t0, const int32_t *len,
+                               int64_t M, int32_t S, int32_t E, int32_t T, const float *obs_tm, const float *act_tm,
+                               const float *logp_tm, const float *ret_tm, const double *rew_tm,
+                               const mhppo_bucket_dst *dst, double *rew_sums, void *work, void *stream);
+
 const char *mhppo_last_error(void);
 const char *mhppo_version(void);
 

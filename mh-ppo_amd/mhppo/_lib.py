@@ -68,6 +68,14 @@ class AdamGate(ctypes.Structure):  # mhppo_adam_gate
     _fields_ = [("kl", P), ("limit", F64), ("stop", P), ("epoch", I32), ("reserved", I32)]
 
 
+class Decision(ctypes.Structure):  # mhppo_decision
+    _fields_ = [("a_d", P), ("logp_d", P), ("probs", P), ("feat_d", P), ("closest", P), ("exist", P)]
+
+
+class Lanes(ctypes.Structure):  # mhppo_lanes
+    _fields_ = [("d", Decision), ("ep_min", P), ("t0", P), ("len", P), ("cur", P)]
+
+
 # name: (restype, argtypes)
 _SIGS = {
     "mhppo_env_create": (I32, [ctypes.POINTER(EnvCfg), I32, ctypes.POINTER(P)]),
@@ -150,6 +158,13 @@ _SIGS = {
     "mhppo_returns_scan_tm_boot": (I32, [P, P, I64, I32, F64, P, P, P]),
     "mhppo_gae_tm_boot": (I32, [ctypes.POINTER(Mlp), ctypes.POINTER(Mlp), P, P, P, P, I64, I32, F64, F64, P, P, P, P,
                                 P]),
+    "mhppo_lanes_begin": (I32, [ctypes.POINTER(Lanes), I32, I64, I32, I32, I32, ctypes.POINTER(Decision), P]),
+    "mhppo_lanes_restart": (I32, [ctypes.POINTER(Lanes), I32, I64, I32, I32, I32, I32, I32, ctypes.POINTER(Decision),
+                                  ctypes.POINTER(Decision), P]),
+    "mhppo_lanes_record": (I32, [ctypes.POINTER(Lanes), I32, I64, I32, I32, I32] + [P] * 11),
+    "mhppo_lanes_close": (I32, [ctypes.POINTER(Lanes), I32, I64, I32, I32, P, P, P]),
+    "mhppo_returns_scan_tm_lanes": (I32, [P, P, I64, I32, I32, I32, F64, P, P, P, P, P, P]),
+    "mhppo_bucket_scatter_lanes": (I32, [P, P, P, P, I64, I32, I32, I32] + [P] * 9),
     "mhppo_last_error": (ctypes.c_char_p, []),
     "mhppo_version": (ctypes.c_char_p, []),
 }

@@ -473,8 +473,8 @@ class Algo_PPO:
             self._after_collect(ep)
         self._finish_train()
 
-    def train_external(self, sim, nb_loop, M, T=None, early_end=False, check_every=None, bootstrap=False,
-                       cut_truncates=True):
+    def train_external(self, sim, nb_loop, M, T=None, early_end=None, check_every=None, bootstrap=False,
+                       cut_truncates=True, auto_reset=None):
         """train() with the rollout replaced (opt-in, beyond the reference): every iteration plays one
         episode of M parallel streams in `sim` -- anything with reset() -> obs float32 [M, obs_dim] and
         step(actions float64 [M, 2S]) -> (obs, rew, rew_light, ...) on this algo's device -- through
@@ -489,20 +489,39 @@ class Algo_PPO:
         bootstrap=True (needs early_end=True): step's fifth value is the per-stream truncated, and an
         episode that was truncated -- at a done flagged so, or still running at the T-step cut unless
         cut_truncates=False -- starts its cross / wait targets from V(s_L) under the current critics
-        instead of 0 (ExternalRollout(bootstrap=True), bucket_segments(boot=...)).  Under data
-        parallelism every rank feeds its own simulator shard."""
+        instead of 0 (ExternalRollout(bootstrap=True), bucket_segments(boot=...)).
+        auto_reset=E (an integer >= 1; needs no early_end=True, and early_end=False with it raises): the
+        simulator resets a stream the moment it reports done, and every stream plays up to E episodes
+        inside the T-step window, each with its own choice decision, bucket and targets
+        (ExternalRollout(auto_reset=E)); step returns no truncated, and with bootstrap=True only the
+        episodes cut at the window's end are bootstrapped.  Out of scope, each a ValueError: gae_lambda
+        together with auto_reset, a mid-window truncated flag, next-step auto-reset simulators, a per-slot
+        done and the compact record layout.  Under data parallelism every rank feeds its own simulator
+        shard."""
         from .external import ExternalRollout
         r = self.rollout
         r.fix_bucket = self.fix_bucket
         lam = getattr(self, "gae_lambda", None)
         r.gae = None if lam is None else (self.critic_net_cross, self.critic_net_wait, self.gamma, lam)
+        if auto_reset is not None:
+            # checked before it goes into the cache key: True, 1 and 1.0 hash alike
+            if isinstance(auto_reset, bool) or not isinstance(auto_reset, int) or auto_reset < 1:
+                raise ValueError(f"train_external: auto_reset is None or an integer >= 1, not {auto_reset!r}")
+            if early_end is not None and not early_end:
+                raise ValueError("train_external: auto_reset implies early_end: early_end=False with it is a contradiction")
+            if lam is not None:
+                raise ValueError("train_external: gae_lambda together with auto_reset is out of scope (the "
+                                 "lambda-return kernel takes one length per column)")
+            early_end = True
         if bootstrap and not early_end:
             raise ValueError("train_external: bootstrap=True needs early_end=True")
-        # cut_truncates means nothing without bootstrap: the key is then the one it was
+        # cut_truncates means nothing without bootstrap, auto_reset nothing when unset: the key is then the one it was
         key = (int(M), int(T or self.max_steps), bool(early_end)) + ((True, bool(cut_truncates)) if bootstrap else ())
+        key += () if auto_reset is None else (("auto_reset", auto_reset),)
         if getattr(self, "_external", None) is None or self._external[0] != key:
             self._external = (key, ExternalRollout(self.policy(), key[0], T=key[1], early_end=key[2],
-                                                   bootstrap=bool(bootstrap), cut_truncates=bool(cut_truncates)))
+                                                   bootstrap=bool(bootstrap), cut_truncates=bool(cut_truncates),
+                                                   auto_reset=auto_reset))
         # the critics are read when the buckets are built, before the iteration's update
         boot = (self.critic_net_cross, self.critic_net_wait) if bootstrap else None
         ext = self._external[1]

@@ -25,6 +25,7 @@ from .policy import noise_key
 
 NF_C = 13
 _CTR_STEP = 1 << 40  # counter stride between time steps (global env*slot index below it)
+GAMMA = 0.99  # the reward-to-go's discount in bucket_segments (futur_rewards, :668-672): every bucketing path's
 
 
 class RolloutBatch:
@@ -385,7 +386,7 @@ def _check_v_boot(v_boot, B, dev, who):
     return v_boot.reshape(B).contiguous()
 
 
-def returns_scan_tm(rew_tm, gamma=0.99, len_rec=None, v_boot=None):
+def returns_scan_tm(rew_tm, gamma=GAMMA, len_rec=None, v_boot=None):
     """futur_rewards over time-major records: rew float64 [T, ...] (one segment per column)
     -> float32 [T, ...].  len_rec int32 [B] (early episode ends, mhppo_returns_scan_tm_len): column b
     has len_rec[b] steps (clamped to [0, T]); its scan starts from G = 0 at its last step -- the early
@@ -576,7 +577,16 @@ def bucket_segments(batch, fix_bucket=False, status=None, gae=None, boot=None):
     boot = (critic_cross, critic_wait) (opt-in, ragged batches only: ExternalRollout(bootstrap=True)): a
     segment whose episode was truncated (batch.trunc at a done, batch.cut_truncates at the cut) starts
     its reward-to-go or GAE scan from V(s_L) under its bucket's critic instead of 0 (boot_values).
+
+    A batch with auto-reset lanes (batch.lanes = E: ExternalRollout(auto_reset=E)) takes
+    bucket_segments_lanes_native / _torch: one segment per (lane, slot), rows in lane-segment order, the
+    dicts' keys those of the ragged path.  gae with such a batch raises (the lambda-return kernel takes
+    one length per column); boot bootstraps the lanes cut when the batch was taken.
     """
+    if getattr(batch, "lanes", None) is not None:  # auto-reset: several episodes per stream
+        if batch.a_d.device.type == "cuda":
+            return bucket_segments_lanes_native(batch, fix_bucket, status, gae=gae, boot=boot)
+        return bucket_segments_lanes_torch(batch, fix_bucket, status, gae=gae, boot=boot)
     if getattr(batch, "len", None) is not None:  # early episode ends: ragged buckets
         if batch.a_d.device.type == "cuda":
             return bucket_segments_ragged_native(batch, fix_bucket, status, gae=gae, boot=boot)
@@ -1018,13 +1028,18 @@ def scatter_sums_torch(rew_tm, own, bucket):
     own bool [T, NS] (the record is scattered), bucket int8 [NS].  A block is 64 segments x 16 steps;
     each step's wave adds its 64 records by the xor butterfly, the block its 16 waves in index order;
     the partials (block y gridDim.x + x) are folded by k_fold<1024, 4>.  -> float64 [2]"""
+    return _scatter_sums_sel(rew_tm, [own & ((bucket != 0) == bool(k))[None, :] for k in range(2)])
+
+
+def _scatter_sums_sel(rew_tm, sels):
+    """scatter_sums_torch with each bucket's records given as a bool [T, NS] mask (the lanes scatter: a
+    column's bucket can change from one episode to the next)."""
     T, NS = rew_tm.shape
     dev = rew_tm.device
     gx, gy = -(-NS // 64), -(-T // 16)
     lanes = torch.arange(64, device=dev)
     out = []
-    for k in range(2):
-        sel = own & ((bucket != 0) == bool(k))[None, :]
+    for sel in sels:
         r = torch.zeros((gy * 16, gx * 64), dtype=torch.float64, device=dev)
         r[:T, :NS] = torch.where(sel, 0.0 + rew_tm.float().double(), torch.zeros((), dtype=torch.float64, device=dev))
         v = r.reshape(gy, 16, gx, 64)
@@ -1120,6 +1135,208 @@ def bucket_segments_ragged_torch(batch, fix_bucket=False, status=None, plan_out=
     n_cross, n_wait, n_all, rows_cross, rows_wait = sizes[:5]
     cross_r, wait_r = _ragged_views(both, rows_cross, rows_wait, n_cross, n_wait)
     choice = {k_: v[:n_all] for k_, v in choice.items()}
+    choice["n_seg"] = n_all
+    choice["counts"] = counts
+    choice["rew_sums"] = rew_sums
+    return cross_r, wait_r, choice
+
+
+# ------------------------------------------------------------------ auto-reset lanes
+def _lanes_fields(batch):
+    """(E, M, S, T, k, t0, len, cut, plan view) of a batch with auto-reset lanes, checked.  The plan view
+    is the batch as mhppo_bucket_plan and the torch bucket rule take it: one "env" per lane, N = E M."""
+    E, M, S, T = int(batch.lanes), int(batch.M), batch.S, batch.T
+    k = int(getattr(batch, "steps", T))
+    dev = batch.a_d.device
+    if E < 1 or not 1 <= k <= T:
+        raise ValueError(f"a lanes batch has lanes >= 1 and 1 <= steps <= T = {T}, not {E}, {k}")
+    out = []
+    for name, dt in (("t0", torch.int32), ("len", torch.int32), ("cut", torch.uint8)):
+        x = getattr(batch, name, None)
+        if not torch.is_tensor(x) or x.dtype != dt or x.numel() != E * M or x.device != dev:
+            raise ValueError(f"a lanes batch's {name} is a {dt} [{E * M}] tensor on the batch's device")
+        out.append(x.reshape(E * M).contiguous())
+    view = RolloutBatch(N=E * M, S=S, P=batch.P, T=T, a_d=batch.a_d, closest=batch.closest, exist=batch.exist,
+                        ep_min=batch.ep_min, feat_d=batch.feat_d, logp_d=batch.logp_d, rec_of=None)
+    return (E, M, S, T, k, *out, view)
+
+
+def _lane_columns(E, M, S, dev):
+    """per lane-segment q = v S + i, v = e M + r: (v, the record column r S + i)"""
+    q = torch.arange(E * M * S, device=dev)
+    v = torch.div(q, S, rounding_mode="floor")
+    return v, (v % M) * S + q % S
+
+
+def returns_scan_tm_lanes_torch(rew_tm, M, S, E, gamma, pos, t0, len, cut, v_boot=None):
+    """mhppo_returns_scan_tm_lanes in torch ops (any device): rew_tm float64 [T, M S] -> float32 [T, M S].
+    Lane-segment q = v S + i with pos[q] >= 0 scans column r S + i over t = t0[v] + L - 1 .. t0[v] in float64,
+    L = len[v], from G = float64(v_boot[col]) where cut[v] and v_boot is given, else 0; every record in no
+    used lane is 0."""
+    T = rew_tm.shape[0]
+    NS = M * S
+    rew = rew_tm.reshape(T, NS)
+    dev = rew.device
+    v, col = _lane_columns(E, M, S, dev)
+    used = pos.reshape(-1) >= 0
+    T0 = t0.long()[v].clamp(0, T)
+    L = torch.minimum(len.long()[v].clamp_min(0), T - T0)
+    g = torch.zeros(v.numel(), dtype=torch.float64, device=dev)
+    if v_boot is not None:
+        g = torch.where(used & (cut[v] != 0) & (L > 0), v_boot.reshape(NS)[col].double(), g)
+    ret = torch.zeros((T, NS), dtype=torch.float32, device=dev)
+    for j in range(T - 1, -1, -1):  # the lane's own step j, wall-clock t0 + j
+        on = used & (j < L)
+        tt = (T0 + j).clamp_max(T - 1)
+        g = torch.where(on, rew[tt, col] + gamma * g, g)
+        ret[tt[on], col[on]] = g[on].float()
+    return ret.reshape(rew_tm.shape)
+
+
+def returns_scan_tm_lanes(rew_tm, M, S, E, gamma, pos, t0, len, cut, v_boot=None):
+    """mhppo_returns_scan_tm_lanes (CUDA): returns_scan_tm_lanes_torch's result, a memset and one launch
+    on the current stream."""
+    T = rew_tm.shape[0]
+    r = rew_tm.reshape(T, M * S).contiguous()
+    out = torch.empty(r.shape, dtype=torch.float32, device=r.device)
+    if v_boot is not None:
+        v_boot = _check_v_boot(v_boot, M * S, r.device, "returns_scan_tm_lanes")
+    p = _lib.ptr
+    with torch.cuda.device(r.device):
+        _lib.check(_lib.lib().mhppo_returns_scan_tm_lanes(p(r), p(out), M, S, E, T, gamma, p(pos), p(t0), p(len), p(cut),
+                                                          p(v_boot), _lib.stream_ptr(device=r.device)))
+    return out.reshape(rew_tm.shape)
+
+
+def _lanes_boot(batch, boot, pos, bucket, E, M, S, k, cut, native):
+    """v_boot float32 [M S] per record column of a lanes batch under boot = (critic_cross, critic_wait), or
+    None without boot: mhppo_boot_values over the M streams, each with the pos / bucket of its open lane
+    (the one cut when the batch was taken; -1 where the stream has none), len = 0 -- every stream then
+    counts as cut at k -- and the batch's cut_truncates and feat_tail."""
+    if boot is None:
+        return None
+    dev = pos.device
+    c = cut.reshape(E, M)
+    v_open = c.to(torch.int64).argmax(0) * M + torch.arange(M, device=dev)  # at most one lane of a stream is open
+    q = v_open[:, None] * S + torch.arange(S, device=dev)[None, :]
+    pos_open = torch.where((c != 0).any(0)[:, None], pos[q], torch.full_like(q, -1)).reshape(M * S)
+    f = boot_values if native else boot_values_torch
+    return f(boot[0], boot[1], pos_open, bucket[q].reshape(M * S).contiguous(), None,
+             torch.zeros(M, dtype=torch.int32, device=dev), torch.zeros(M, dtype=torch.uint8, device=dev), M, S, k,
+             getattr(batch, "cut_truncates", True), batch.obs_c_tm, getattr(batch, "feat_tail", None))
+
+
+def _lanes_no_gae(gae):
+    if gae is not None:
+        raise ValueError("bucket_segments: gae (gae_lambda) with auto-reset lanes is out of scope: the "
+                         "lambda-return kernel takes one length per column")
+
+
+def bucket_segments_lanes_native(batch, fix_bucket=False, status=None, gae=None, boot=None):
+    """bucket_segments on the GPU for a batch with auto-reset lanes (ExternalRollout(auto_reset=E)):
+    mhppo_bucket_plan and mhppo_ragged_plan over the N = E M lanes with the lanes' len (a lane never
+    started has exist = 0, hence pos < 0 and no row), mhppo_boot_values for the lanes cut at the window's
+    end (boot), mhppo_returns_scan_tm_lanes over the wall-clock records, and ONE scatter of both buckets
+    into the shared buffer that also folds the cross / wait reward sums (mhppo_bucket_scatter_lanes).
+    Cross rows start at row 0, wait rows at W0 = rows_cross rounded up to a multiple of 4; segments follow
+    the lane-segment order (lane e, stream r, slot i), a lane-segment of length L owns L contiguous rows;
+    the choice batch has one row per existing lane-segment in that order, ret = (float)ep_min of the lane.
+    The dicts' keys are the ragged path's; the one host read comes before the scatter is queued."""
+    _lanes_no_gae(gae)
+    E, M, S, T, k, t0, ln, cut, view = _lanes_fields(batch)
+    NS = M * S
+    dev = batch.a_d.device
+    L = _lib.lib()
+    plan = bucket_plan(view, fix_bucket, status)
+    row0, _, rinfo = ragged_plan(plan["pos"], plan["bucket"], None, ln, E * M, S, k)
+    v_boot = _lanes_boot(batch, boot, plan["pos"], plan["bucket"], E, M, S, k, cut, native=True)
+    ret_tm = returns_scan_tm_lanes(batch.rew_tm, M, S, E, GAMMA, plan["pos"], t0, ln, cut, v_boot)
+    info = plan["info"]
+    n = NS * T + 3  # a stream's lanes do not overlap: at most k rows per column
+    both = dict(obs=torch.empty(n, NF_C, dtype=torch.float32, device=dev),
+                act=torch.empty(n, dtype=torch.float32, device=dev),
+                logp=torch.empty(n, dtype=torch.float32, device=dev),
+                ret=torch.empty(n, dtype=torch.float32, device=dev),
+                rew=torch.empty(n, dtype=torch.float64, device=dev))
+    one = _lib.BucketDst(*[both[k_].data_ptr() for k_ in ("obs", "act", "logp", "ret", "rew")])
+    dst = (_lib.BucketDst * 2)(one, one)  # cross and wait rows share the buffer (bucket[] keys the sums)
+    srcs = [x.contiguous() for x in (batch.obs_c_tm, batch.act_tm, batch.logp_tm)]
+    rew_tm = batch.rew_tm.contiguous()
+    p = _lib.ptr
+    args = (p(row0), p(plan["bucket"]), p(t0), p(ln), M, S, E, T, *[p(x) for x in srcs], p(ret_tm), p(rew_tm), dst,
+            ctypes.c_void_p(info.data_ptr() + 48), p(plan["work"]), _lib.stream_ptr(device=dev))
+    n_cross, n_wait, n_all, st, rows_cross, rows_wait = torch.cat([info[:4], rinfo]).tolist()  # the one host read
+    if status is not None:
+        if st:
+            status.zero_()
+        raise_if_nan_status(st)
+    with torch.cuda.device(dev):
+        _lib.check(L.mhppo_bucket_scatter_lanes(*args))
+    cross_r, wait_r = _ragged_views(both, rows_cross, rows_wait, n_cross, n_wait)
+    choice = {k_: plan[k_][:n_all] for k_ in ("obs", "act", "logp", "ret")}
+    choice["n_seg"] = n_all
+    f64 = info[4:9].view(torch.float64)
+    choice["counts"] = f64[0:2]
+    choice["rew_sums"] = f64[2:5]
+    return cross_r, wait_r, choice
+
+
+def bucket_segments_lanes_torch(batch, fix_bucket=False, status=None, plan_out=None, gae=None, boot=None):
+    """bucket_segments_lanes_native in torch ops (any device): its specification and the CPU path.
+    Everything is queued before the one host read.  plan_out: a dict that receives pos, bucket, row0, ret_tm
+    and v_boot (tests)."""
+    _lanes_no_gae(gae)
+    E, M, S, T, k, t0, ln, cut, view = _lanes_fields(batch)
+    NS, NL = M * S, E * M * S
+    exist, cross, wait = _segment_masks(view, fix_bucket)
+    dev = exist.device
+    cc, cw = torch.cumsum(cross, 0), torch.cumsum(wait, 0)
+    n_cross_d = cc[-1] if NL else torch.zeros((), dtype=torch.int64, device=dev)
+    w0s = torch.div(n_cross_d + 3, 4, rounding_mode="floor") * 4
+    pos = torch.where(cross, cc - 1, torch.where(wait, w0s + cw - 1, -1))
+    bucket = wait.to(torch.int8)
+    row0, _, rinfo = ragged_plan_torch(pos, bucket, None, ln, E * M, S, k)
+    v_boot = _lanes_boot(batch, boot, pos, bucket, E, M, S, k, cut, native=False)
+    rew_tm = batch.rew_tm.reshape(T, NS)
+    obs_tm = batch.obs_c_tm.reshape(T, NS, NF_C)
+    ret_tm = returns_scan_tm_lanes_torch(rew_tm, M, S, E, GAMMA, pos, t0, ln, cut, v_boot)
+    if plan_out is not None:
+        plan_out.update(pos=pos, bucket=bucket, row0=row0, ret_tm=ret_tm, v_boot=v_boot)
+    # record (t0 + j, col) of a used lane-segment goes to row row0 + j, j < len; every other pair (j, q) to
+    # a spare row past the buffer's end
+    n = NS * T + 3
+    v, col = _lane_columns(E, M, S, dev)
+    jj = torch.arange(T, device=dev)[:, None]
+    own = (row0 >= 0)[None, :] & (jj < ln.long()[v][None, :])  # [T, NL]
+    rows = torch.where(own, row0[None, :] + jj, n).reshape(-1)
+    rec = torch.where(own, (t0.long()[v][None, :] + jj) * NS + col[None, :], 0).reshape(-1)
+    both = {}
+    for key, x, dt in (("obs", obs_tm, torch.float32), ("act", batch.act_tm, torch.float32),
+                       ("logp", batch.logp_tm, torch.float32), ("ret", ret_tm, torch.float32),
+                       ("rew", rew_tm, torch.float64)):
+        x = x.reshape(T * NS, -1)
+        buf = torch.zeros((n + 1, x.shape[1]), dtype=dt, device=dev)
+        buf[rows] = x[rec]
+        both[key] = buf[:n] if key == "obs" else buf[:n, 0]
+    # the reward sums, in the fixed orders of mhppo_bucket_scatter_lanes and mhppo_bucket_plan
+    sels = []
+    for b in range(2):
+        m = torch.zeros(T * NS + 1, dtype=torch.bool, device=dev)
+        m[torch.where(own & ((bucket != 0) == bool(b))[None, :], rec.reshape(T, NL), T * NS).reshape(-1)] = True
+        sels.append(m[:T * NS].reshape(T, NS))
+    choice, counts = _choice_torch(view, exist)
+    rew_sums = torch.cat([_scatter_sums_sel(rew_tm, sels), plan_ep_sum_torch(batch.ep_min, exist).reshape(1)])
+    sizes = [n_cross_d, cw[-1] if NL else n_cross_d, exist.sum(), rinfo[0], rinfo[1]]
+    if status is not None:
+        sizes.append(status.reshape(-1)[0].to(torch.int64))
+    sizes = torch.stack(sizes).tolist()  # the one host read
+    if status is not None:
+        if sizes[5]:
+            status.zero_()
+        raise_if_nan_status(sizes[5])
+    n_cross, n_wait, n_all, rows_cross, rows_wait = sizes[:5]
+    cross_r, wait_r = _ragged_views(both, rows_cross, rows_wait, n_cross, n_wait)
+    choice = {k_: x[:n_all] for k_, x in choice.items()}
     choice["n_seg"] = n_all
     choice["counts"] = counts
     choice["rew_sums"] = rew_sums
